@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark: train-step frames/sec + DDIM steps/sec, 128x128x16 UNet3D (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+    A plain run does what the headline needs and nothing else: it builds the model, runs W
+    untimed and K timed train steps, writes the last step's outputs with --dump-outputs, and
+    prints one JSON line (metric / value / unit / higher_is_better / dtype / ms_per_step, the
+    per-launch attention figures of the timed steps).  --full adds every other leg described
+    below: the DDIM legs, config 4, the cross-attention and spatial_temporal train legs, the
+    ViViT leg, the extra train step of the per-launch conv breakdown and the CPU baselines.
+    Without --full the options of those legs (--ddim-steps, --c4-steps, --xattn-steps,
+    --st-steps, --vivit-*, --no-cpu, --cpu-frames) are accepted and change nothing; --only
+    ddim / ddim_st / vivit and --train-graph, which ask for such a leg by name, are refused.
+    --dump-outputs DIR: what the last timed train step handed its caller -- the loss and the
+    updated parameters -- as DIR/<name>.npy (OutputDump below); the inputs are seeded, so
+    two builds run with the same arguments can be compared array for array.
     N > 1 without a launcher: the process starts `python -m torch.distributed.run
     --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
     itself (before anything touches the GPU) and exits with its status; under an external
@@ -62,6 +74,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline train steps: DDIM (joint, "
+                         "spatial_temporal, config 4), the audio cross-attention and "
+                         "spatial_temporal train legs, ViViT, --train-graph, the per-launch conv "
+                         "breakdown (one extra train step) and the CPU baselines; the options "
+                         "of those legs have no effect without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed train step returned (loss, updated "
+                         "parameters) as DIR/<name>.npy after the timed steps (OutputDump)")
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--clips-per-gpu", type=int, default=1)
@@ -115,7 +136,12 @@ def parse():
     ap.add_argument("--init", choices=["nonzero", "reference"], default="nonzero",
                     help="train-leg init: 'nonzero' re-initialises the reference's zero_module "
                          "layers (engine.reinit_nonzero); 'reference' keeps train.py's init")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.only not in ("train", "all") or args.train_graph):
+        ap.error("--only ddim / ddim_st / vivit and --train-graph select legs of --full")
+    if args.dump_outputs and args.only not in ("train", "all"):
+        ap.error("--dump-outputs writes the train leg's outputs: --only train or all")
+    return args
 
 
 def log(*a):
@@ -159,6 +185,75 @@ def clip_bank(args, n, device, seed):
     from vdiff.engine import synthetic_clip
     return [synthetic_clip(args.clips_per_gpu, args.frames, args.size, 100, device,
                            seed=seed * 1000 + i) for i in range(n)]
+
+
+DUMP_SEED = 2024
+DUMP_PER_TENSOR = 4096  # sampled elements of each parameter tensor (3.7 MB per sample file here)
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+class OutputDump:
+    """--dump-outputs DIR: what a caller of the timed path (Trainer.step) holds after the last
+    timed step -- the loss it returned and the parameters it updated -- as DIR/<name>.npy:
+      loss.npy               [1] float32, the loss of the last timed step
+      train_losses.npy       [W + K] float32, every step's loss, warm-up first
+      param_norms.npy        [tensors] float64, the L2 norm of every parameter tensor (all
+                             elements), in model.named_parameters() order
+      param_sample.npy       float32, a fixed seeded sample of the updated parameters (the
+                             model holds ~0.5 GB of them): of each tensor, in the same order,
+                             all elements up to DUMP_PER_TENSOR, else DUMP_PER_TENSOR elements
+                             at indices drawn from a generator of its own (DUMP_SEED)
+      param_delta_sample.npy float32, the same elements minus their values before the first
+                             warm-up step: the sum of the run's Adam updates, which shows a
+                             wrong gradient where the parameter values alone would hide it
+    Built before the first step (it keeps the sampled initial values); it draws nothing from
+    the global generators, so the steps run as they do without it.
+    Noise floor: the inputs and the initial weights are the same in every run, but the
+    backward is not bit-reproducible from process to process, and Adam's first steps move a
+    parameter by about lr whatever the size of its gradient, so a gradient near 0 whose sign
+    differs in the last bit moves its parameter the other way.  Two runs of ONE build (5 timed
+    + 2 warm-up steps, MI355X) agreed bit for bit in the first five losses, to 8e-6 in the
+    rest, to 1e-7 relative in param_norms, to rel-L2 2e-6 in param_sample and to rel-L2 1e-3
+    in param_delta_sample; that last figure grows with the number of steps (1.6e-2 was
+    measured between two longer runs).  At a 32x32x4 clip even the first loss, one forward of
+    the same weights on the same inputs, took the values 1.345303, 1.345259 and 1.345062 in
+    four runs (1.5e-4 relative; cause not located).  Two builds differ only where they differ
+    by more than that."""
+
+    def __init__(self, model, seed=DUMP_SEED, per_tensor=DUMP_PER_TENSOR):
+        g = torch.Generator().manual_seed(seed)
+        self.params = [p for _, p in model.named_parameters()]
+        self.idx = []
+        for p in self.params:
+            n = p.numel()
+            i = torch.arange(n) if n <= per_tensor else torch.randint(0, n, (per_tensor,),
+                                                                      generator=g)
+            self.idx.append(i.to(p.device))
+        self.before = self._sample()
+
+    @torch.no_grad()
+    def _sample(self):
+        return torch.cat([p.detach().reshape(-1)[i].float()
+                          for p, i in zip(self.params, self.idx)]).cpu()
+
+    @torch.no_grad()
+    def write(self, out_dir, losses):
+        """losses: every step's loss so far (floats), the last timed step's at the end."""
+        import numpy as np
+        after = self._sample()
+        norms = torch.stack([p.detach().double().norm() for p in self.params]).cpu()
+        arrays = {"loss": np.asarray(losses[-1:], dtype=np.float32),
+                  "train_losses": np.asarray(losses, dtype=np.float32),
+                  "param_norms": norms.numpy(),
+                  "param_sample": after.numpy(),
+                  "param_delta_sample": (after - self.before).numpy()}
+        total = sum(a.nbytes for a in arrays.values())
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        return total
 
 
 def ddim_stepper(args, model, sampler, cond, feats, xt):
@@ -645,6 +740,32 @@ def graph_leg(args, device):
     return out
 
 
+def conv_breakdown(trainer, clip):
+    """--full: the per-launch conv times of one extra untimed train step (their ~500 event
+    pairs stay out of the timed steps), summed per kernel kind."""
+    from vdiff import ops
+    ctimer = ops.KernelTimer(attention=False, convs=True)
+    ops.set_timer(ctimer)
+    trainer.step(clip)  # untimed: per-launch conv times
+    ops.set_timer(None)
+    conv = ctimer.conv_summary()
+    by_kind = {}
+    for (kind, key), (cnt, tot, flop) in conv.items():
+        a = by_kind.setdefault(kind, [0, 0.0, 0.0])
+        a[0] += cnt
+        a[1] += tot
+        a[2] += flop * cnt
+    out = {
+        k: {"launches": c, "ms_per_step": round(t, 2),
+            "tflops": round(f / (t / 1e3) / 1e12, 1) if t > 0 else None}
+        for k, (c, t, f) in sorted(by_kind.items())}
+    out["note"] = "one extra untimed train step after the timed ones"
+    for (kind, key), (cnt, tot, flop) in sorted(conv.items(), key=lambda kv: -kv[1][1])[:60]:
+        log(f"  conv {kind:16s} {key:40s} x{cnt:<3d} {tot:7.2f} ms/step "
+            f"{flop * cnt / (tot / 1e3) / 1e12:7.1f} TF/s")
+    return out
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -708,7 +829,9 @@ def main():
     broadcast_parameters(model)
     # the DDIM / config-4 legs time the benchmark init (reinit_nonzero), not the weights the
     # train leg's Adam steps leave behind
-    if args.init == "nonzero":
+    if not args.full:
+        init_state = None
+    elif args.init == "nonzero":
         init_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
     else:
         init_state = build_model(args, device, init="nonzero").state_dict()
@@ -731,6 +854,7 @@ def main():
     if args.only in ("train", "all"):
         trainer = Trainer(model, sched, lr=args.lr)
         bank = clip_bank(args, args.warmup + args.steps, device, rank)
+        dump = OutputDump(model) if args.dump_outputs and rank == 0 else None
         for i in range(args.warmup):
             loss = trainer.step(bank[i])
             train_losses.append(loss)
@@ -749,6 +873,11 @@ def main():
         barrier_sync(world)
         el = time.perf_counter() - t0
         ops.set_timer(None)
+        if dump is not None:
+            nbytes = dump.write(args.dump_outputs, [float(x) for x in train_losses])
+            log(f"outputs of the last timed step: {nbytes / 2 ** 20:.1f} MB of .npy files in "
+                f"{args.dump_outputs}")
+            del dump
         if trainer.bucketer is not None:
             trainer.bucketer.timing = False
             result["allreduce"] = comm_report(trainer, world, device, args.steps)
@@ -782,25 +911,8 @@ def main():
             f"model {result['model_tflops_per_gpu']} TFLOP/s/GPU (3x fwd)")
         for r in rows:
             log("  kernel", r)
-        ctimer = ops.KernelTimer(attention=False, convs=True)
-        ops.set_timer(ctimer)
-        trainer.step(bank[-1])  # untimed: per-launch conv times
-        ops.set_timer(None)
-        conv = ctimer.conv_summary()
-        by_kind = {}
-        for (kind, key), (cnt, tot, flop) in conv.items():
-            a = by_kind.setdefault(kind, [0, 0.0, 0.0])
-            a[0] += cnt
-            a[1] += tot
-            a[2] += flop * cnt
-        result["conv_kernels"] = {
-            k: {"launches": c, "ms_per_step": round(t, 2),
-                "tflops": round(f / (t / 1e3) / 1e12, 1) if t > 0 else None}
-            for k, (c, t, f) in sorted(by_kind.items())}
-        result["conv_kernels"]["note"] = "one extra untimed train step after the timed ones"
-        for (kind, key), (cnt, tot, flop) in sorted(conv.items(), key=lambda kv: -kv[1][1])[:60]:
-            log(f"  conv {kind:16s} {key:40s} x{cnt:<3d} {tot:7.2f} ms/step "
-                f"{flop * cnt / (tot / 1e3) / 1e12:7.1f} TF/s")
+        if args.full:
+            result["conv_kernels"] = conv_breakdown(trainer, bank[-1])
         del trainer, bank
         torch.cuda.empty_cache()
 
@@ -812,7 +924,7 @@ def main():
         result.update(value=result["ddim_st"]["value"], unit="steps/s",
                       ms_per_step=result["ddim_st"]["ms_per_step"])
 
-    if args.only in ("ddim", "all"):
+    if args.full and args.only in ("ddim", "all"):
         with torch.no_grad():
             model.load_state_dict(init_state)
         kd = args.ddim_steps or args.steps
@@ -876,7 +988,7 @@ def main():
         if "value" not in result:
             result.update(value=ddim["value"], unit="steps/s", ms_per_step=ddim["ms_per_step"])
 
-    if args.only in ("train", "all") and args.xattn_steps != 0:
+    if args.full and args.only in ("train", "all") and args.xattn_steps != 0:
         try:  # an auxiliary leg: never let it take the headline numbers down
             result["audio_xattn"] = xattn_leg(args, rank, world, device,
                                               result.get("ms_per_step"))
@@ -884,21 +996,22 @@ def main():
             log(f"xattn leg failed: {type(e).__name__}: {e}")
             result["audio_xattn"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
 
-    if args.only in ("train", "all") and args.st_steps != 0 and args.mode == "joint":
+    if (args.full and args.only in ("train", "all") and args.st_steps != 0
+            and args.mode == "joint"):
         try:  # an auxiliary leg: never let it take the headline numbers down
             result["spatial_temporal"] = st_leg(args, rank, world, device)
         except Exception as e:
             log(f"spatial_temporal leg failed: {type(e).__name__}: {e}")
             result["spatial_temporal"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
 
-    if args.only in ("train", "all") and args.train_graph and world == 1:
+    if args.full and args.only in ("train", "all") and args.train_graph and world == 1:
         try:  # an auxiliary leg: never let it take the headline numbers down
             result["train_graph"] = graph_leg(args, device)
         except Exception as e:
             log(f"train graph leg failed: {type(e).__name__}: {e}")
             result["train_graph"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
 
-    if args.only in ("vivit", "all") and args.vivit_steps > 0:
+    if args.full and args.only in ("vivit", "all") and args.vivit_steps > 0:
         try:  # an auxiliary leg: never let it take the headline numbers down
             result["vivit"] = vivit_leg(args, rank, world, device)
         except Exception as e:
@@ -914,7 +1027,7 @@ def main():
         "fwd_tflop_per_clip": round(work.total / 1e12, 3)}
     if rows:
         result["kernels"] = rows
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             result["cpu_baseline"] = cpu_baseline(args)
         except Exception as e:  # never let the baseline leg kill the GPU numbers

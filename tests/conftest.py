@@ -43,9 +43,15 @@ def record_metric(**kw):
 
 
 def golden(name):
+    """The arrays of fixture `name` (<stem>.npz).  A set too large for one committed file is
+    stored as <stem>.part0.npz, <stem>.part1.npz, ... (gen_golden.save) and merged here."""
     if name not in _cache:
-        with np.load(os.path.join(GOLDEN, name), allow_pickle=False) as z:
-            _cache[name] = {k: torch.from_numpy(z[k].copy()) for k in z.files}
+        import glob
+        parts = sorted(glob.glob(os.path.join(GOLDEN, name[:-len(".npz")] + ".part*.npz")))
+        _cache[name] = {}
+        for path in parts or [os.path.join(GOLDEN, name)]:
+            with np.load(path, allow_pickle=False) as z:
+                _cache[name].update({k: torch.from_numpy(z[k].copy()) for k in z.files})
     return _cache[name]
 
 

@@ -47,11 +47,34 @@ def npy(t):
         t.detach().cpu().numpy()
 
 
+PART_BYTES = 1000000  # no fixture file above 1 MiB: a larger set is split into parts
+
+
+def _npz_bytes(arrs):
+    import io
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrs)
+    return buf.getvalue()
+
+
 def save(name, **arrs):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **{k: npy(v) if torch.is_tensor(v) else np.asarray(v)
-                                 for k, v in arrs.items()})
-    print("wrote", path, os.path.getsize(path), "bytes")
+    """<name> as one .npz, or, above PART_BYTES, as <stem>.part0.npz, <stem>.part1.npz, ...
+    with the arrays in order (tests/conftest.py's golden() merges them)."""
+    import glob
+    arrs = {k: npy(v) if torch.is_tensor(v) else np.asarray(v) for k, v in arrs.items()}
+    stem = os.path.join(HERE, name[:-len(".npz")])
+    for old in glob.glob(stem + ".part*.npz") + glob.glob(stem + ".npz"):
+        os.remove(old)
+    parts = [{}]
+    for k, v in arrs.items():
+        if parts[-1] and len(_npz_bytes({**parts[-1], k: v})) > PART_BYTES:
+            parts.append({})
+        parts[-1][k] = v
+    for i, part in enumerate(parts):
+        path = stem + (".npz" if len(parts) == 1 else f".part{i}.npz")
+        with open(path, "wb") as f:
+            f.write(_npz_bytes(part))
+        print("wrote", path, os.path.getsize(path), "bytes")
 
 
 def load_init(module, seed):

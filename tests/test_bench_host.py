@@ -78,3 +78,72 @@ def test_bench_cli_defaults():
         sys.argv = argv
     assert (a.gpus, a.steps, a.warmup, a.frames, a.size, a.dtype) == (1, 3, 1, 16, 128, "bf16")
     assert a.vivit_batch == 16 and a.only == "all"
+    assert a.full is False and a.dump_outputs is None  # a plain run: the headline steps only
+
+
+def _parse(b, *argv):
+    import sys
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py", *argv]
+        return b.parse()
+    finally:
+        sys.argv = old
+
+
+def test_bench_cli_full_only_legs_need_full(capsys):
+    """The legs that moved behind --full are refused by name without it (never run silently
+    as nothing), and --dump-outputs goes with the train leg only."""
+    b = _bench()
+    for argv in (["--only", "ddim"], ["--only", "ddim_st"], ["--only", "vivit"],
+                 ["--train-graph"], ["--full", "--only", "ddim", "--dump-outputs", "d"]):
+        with pytest.raises(SystemExit) as e:
+            _parse(b, *argv)
+        assert e.value.code == 2, argv
+    capsys.readouterr()
+    a = _parse(b, "--full", "--only", "vivit")
+    assert a.full and a.only == "vivit"
+    a = _parse(b, "--only", "train", "--dump-outputs", "d", "--steps", "7")
+    assert not a.full and a.dump_outputs == "d" and a.steps == 7
+
+
+def test_output_dump_files(tmp_path):
+    """bench.OutputDump on a CPU model: float32 / float64 .npy files, small tensors whole and
+    large ones sampled at the same seeded indices every time, the delta equal to the change of
+    the sampled elements since construction, the norms over all elements."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    def model():
+        torch.manual_seed(3)
+        return torch.nn.Sequential(torch.nn.Linear(300, 100), torch.nn.Linear(100, 7))
+
+    m = model()
+    state = torch.get_rng_state()
+    d = b.OutputDump(m, per_tensor=64)
+    assert torch.equal(torch.get_rng_state(), state)  # draws nothing from the global generator
+    assert [len(i) for i in d.idx] == [64, 64, 64, 7]
+    with torch.no_grad():
+        for k, p in enumerate(m.parameters()):
+            p.add_(0.5 * (k + 1))
+    nbytes = d.write(str(tmp_path / "o"), [1.5, 1.25, 0.75])
+    got = {f[:-4]: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert sorted(got) == ["loss", "param_delta_sample", "param_norms", "param_sample",
+                           "train_losses"]
+    assert nbytes == sum(a.nbytes for a in got.values()) <= b.DUMP_MAX_BYTES
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["loss"].tolist() == [0.75] and got["train_losses"].tolist() == [1.5, 1.25, 0.75]
+    assert got["param_sample"].shape == got["param_delta_sample"].shape == (64 * 3 + 7,)
+    want = np.repeat([0.5, 1.0, 1.5, 2.0], [64, 64, 64, 7])
+    np.testing.assert_allclose(got["param_delta_sample"], want, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(got["param_norms"],
+                               [float(p.detach().double().norm()) for p in m.parameters()],
+                               rtol=1e-12)
+    # a second build of the same model: the same elements
+    m2 = model()
+    d2 = b.OutputDump(m2, per_tensor=64)
+    assert all(torch.equal(i, j) for i, j in zip(d.idx, d2.idx))
+    np.testing.assert_array_equal(d2.before.numpy(), d.before.numpy())
+    np.testing.assert_allclose(got["param_sample"] - got["param_delta_sample"],
+                               d.before.numpy(), rtol=0, atol=1e-6)

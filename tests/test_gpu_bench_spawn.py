@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
 def _run(extra, timeout=300):
     env = dict(os.environ, VDIFF_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full",
+           "--no-cpu"] + extra  # --full: the spatial_temporal and ViViT legs are checked below
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]

@@ -10,7 +10,7 @@ rc=$?
 tail -5 gpurun_out/pytest_gpu.log
 [ $rc -eq 0 ] || { echo "pytest rc=$rc"; grep -E "FAIL|Error|error" gpurun_out/pytest_gpu.log | head -30; exit $rc; }
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 600 python -u bench.py --steps 5 --warmup 2 --c4-steps 1 --vivit-steps 5 \
+  timeout -k 10 600 python -u bench.py --full --steps 5 --warmup 2 --c4-steps 1 --vivit-steps 5 \
     > gpurun_out/bench_short.json 2> gpurun_out/bench_short.err
   rc=$?
   tail -c 3000 gpurun_out/bench_short.json
