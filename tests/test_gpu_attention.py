@@ -6,7 +6,7 @@ import torch
 from oracle import nn as onn
 from oracle.fixtures import rel_l2, seeded
 
-from conftest import golden
+from conftest import golden, record_metric
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -151,3 +151,30 @@ def test_kv_split(C, T, HW):
     from vdiff import ops
     with ops.attention_config("base"):
         _check(1, C, 1, T, HW, "joint", True, torch.bfloat16, 80 + C)
+
+
+@pytest.mark.parametrize("N", [201, 1157])
+@pytest.mark.parametrize("C", [32, 64, 128, 256])
+def test_bf16_rows_and_lse(C, N):
+    """Second check beside test_joint_head_dims / test_bf16_long_ragged_ring (tests/_attn_rows.py):
+    O, dQ, dK and dV separately, worst token row against fp64, within 4 x the same statistic of
+    the CPU emulation of bf16 attention, and lse within 2^-8 max|score| + 1e-5.  Measured on an
+    MI355X, kernel / emulation: O 3.9-6.7e-3 / 3.6-4.8e-3 (at most 1.5 x, head_dim 128 at
+    N = 1157), dQ 4.5-6.8e-3 / 4.6-6.9e-3, dK 4.4-8.1e-3 / 4.4-7.8e-3, dV 4.6-7.3e-3 / the same
+    (at most 1.04 x); lse error 0.07-0.17 of its bound, the emulation's the same.  Both go to
+    record_metric."""
+    from _attn_rows import check
+    if N == 201:
+        check(2, C, 3, 67, "joint", 90 + C, record_metric)
+    else:
+        check(1, C, 1, 1157, "joint", 91 + C, record_metric)
+
+
+@pytest.mark.parametrize("mode,T,HW", [("spatial", 5, 130), ("temporal", 40, 9)])
+def test_bf16_rows_and_lse_groupings(mode, T, HW):
+    """The same per-row check through the spatial regrouping (B * T sequences of HW tokens) and
+    the temporal one on the flash kernels (T = 40 > 32 tokens: not the short path).  Measured,
+    kernel / emulation: O 5.9e-3 / 5.9e-3 and 5.0e-3 / 5.0e-3, dQ 5.1e-3, dK 7.2e-3 / 6.9e-3,
+    dV 7.1e-3 and 6.6e-3 (equal to the emulation); lse 0.13 and 0.23 of the bound."""
+    from _attn_rows import check
+    check(2, 64, T, HW, mode, 95, record_metric)

@@ -157,3 +157,18 @@ def test_backward_with_misaligned_gradient_falls_back_to_flash():
     torch.cuda.synchronize()
     assert grads["aligned"].abs().max() > 0
     assert rel_l2(grads["misaligned"], grads["aligned"]) < 2e-2
+
+
+@pytest.mark.parametrize("T", [9, 17, 25])
+def test_short_rows_and_lse(T):
+    """Second check beside test_ragged_lengths (tests/_attn_rows.py): O, dQ, dK and dV
+    separately, worst token row against fp64, within 4 x the same statistic of the CPU
+    emulation of bf16 attention, and lse within 2^-8 max|score| + 1e-5, on the short kernels
+    (temporal grouping, one sequence per pixel).  Measured on an MI355X, kernel / emulation:
+    O 2.7-3.2e-3 / 4.2-7.0e-3, dQ 3.9-4.3e-3 / 5.5-7.8e-3, dK 4.1-4.4e-3 / 7.6-9.1e-3, dV
+    3.8-4.2e-3 / 6.4-7.9e-3 (the short kernels scale the scores in fp32, so they sit under the
+    emulation, which rounds q scale log2(e) to bf16); lse error 1e-4 of its bound (emulation
+    0.3-0.45).  Both go to record_metric."""
+    from _attn_rows import check
+    assert _uses_short(2, 64, 1, T, 37, "temporal", True)
+    check(2, 64, T, 37, "temporal", 600 + T, record_metric)
