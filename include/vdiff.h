@@ -120,6 +120,38 @@ int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev,
                  const float* acp, float eta, int clip, int64_t B,
                  int64_t per_sample, int dtype, void* stream);
 
+/* ---- classifier-free audio guidance (build extension; no reference counterpart: the
+ * reference samples with one conditional forward per step, test.py:51-83) ----
+ * eps_c / eps_u: the denoiser's noise with the audio and with the null audio, [B][per_sample]
+ * in `dtype`.  g = eps_u + w (eps_c - eps_u) in fp32; with rescale = phi in (0, 1] the guided
+ * noise is f_b g, f_b = phi sqrt(SS(eps_c[b]) / SS(g[b])) + (1 - phi), SS(x) = sum (x_i -
+ * mean(x))^2 over the sample (the std-rescale of Lin et al. 2023, diffusers'
+ * rescale_noise_cfg; the n - 1 of the unbiased std cancels in the ratio); phi = 0: g itself.
+ * vd_cfg_stats: the per-sample statistics in a FIXED order into the caller's workspace
+ * (vd_cfg_workspace_size bytes, [B][partials][4] fp32): per-block sums of fixed ranges, then
+ * per-block CENTRED sums of squares about the mean of the sums added in a fixed order.  Two
+ * launches, no atomics, no semaphore, no memset and no cross-block communication inside a
+ * launch, so the bits are identical eager and replayed from a HIP graph (DESIGN section 9.3,
+ * as vd_mse_loss; torch.std is the one-launch multi-block reduction that went stale there).
+ * vd_ddim_step_cfg: guide, rescale and the vd_ddim_step update in one pass: reads xt, eps_c,
+ * eps_u (and z), writes x_prev and x0 (x0 may be NULL) and, when x_prev_dup is non-NULL, the
+ * same x_prev values there too (the second half of a doubled-batch denoiser input).  x_prev
+ * may alias xt.  rescale > 0 reads the workspace vd_cfg_stats filled for the same eps_c, eps_u
+ * and w; every block adds its sample's partials in the same fixed order.  rescale == 0: workspace
+ * may be NULL and vd_cfg_stats need not run.
+ * vd_cfg_combine: the same guided noise written to eps_out (the eps of vd_p_sample_*). */
+size_t vd_cfg_workspace_size(int64_t B, int64_t per_sample);
+int vd_cfg_stats(const void* eps_c, const void* eps_u, float w, int64_t B, int64_t per_sample,
+                 int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                     void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                     const int64_t* t_prev, const float* acp, float w, float rescale,
+                     const void* workspace, float eta, int clip, int64_t B, int64_t per_sample,
+                     int dtype, void* stream);
+int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w, float rescale,
+                   const void* workspace, int64_t B, int64_t per_sample, int dtype,
+                   void* stream);
+
 /* ---- GroupNorm (+SiLU) -------------------------------------------------
  * replaces GroupNorm32 (utils.py:54-56, fp32 statistics) followed by nn.SiLU
  * (unet.py:194-198, 218-225, 297, 624-628).  x, y: [B][S][C] channels-last,

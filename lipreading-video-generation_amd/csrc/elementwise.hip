@@ -6,6 +6,7 @@
 // schedule scalars from the fp32 tables on device (no host sync on t).
 #include "vd_common.h"
 #include <math.h>
+#include <initializer_list>
 
 namespace {
 
@@ -336,6 +337,197 @@ __global__ void __launch_bounds__(kBlock) mse_bwd_kernel(
   for (int64_t j = nv * 8 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n;
        j += (int64_t)gridDim.x * blockDim.x)
     Elem<T>::st(gpred + j, c * (Elem<T>::ld(pred + j) - Elem<T>::ld(tgt + j)));
+}
+
+// ------------------------------------------------------------ classifier-free audio guidance
+// eps = f_b * g with g = u + w (c - u) (c / u: the denoiser's noise with / without the audio)
+// and, with rescale = phi > 0, f_b = phi sqrt(SS(c) / SS(g)) + (1 - phi) per sample,
+// SS(x) = sum (x_i - mean(x))^2: the std-rescale of Lin et al. 2023 (the n - 1 of the unbiased
+// std cancels in the ratio).  Statistics (vd_cfg_stats): a fixed-order two-pass reduction over
+// the caller's workspace [B][nb][4] fp32.  Block k of sample b owns one fixed contiguous range
+// (a multiple of 8 elements, the last one ragged).  cfg_sum_kernel writes its sums of c and g
+// to slots 0 / 1; the centred pass adds the sample's nb sums (lane k holds partial k, then the
+// same fixed LDS tree: every block the same adds, so the same mean bits), and writes its sums
+// of (c - mean_c)^2 and (g - mean_g)^2 to slots 2 / 3 -- centred, so a sample with |mean| >>
+// sigma loses nothing to cancellation as sum x^2 - (sum x)^2 / P would.  The consumers
+// (cfg_factor) add slots 2 / 3 the same way.
+// No atomics, no memset, no semaphore, no cross-block communication inside a launch: the same
+// bits every run, eager or replayed from a HIP graph (torch's one-launch
+// multi-block reductions -- torch.std is one -- use a hipMemsetAsync'd semaphore plus a
+// last-block combine, which returned stale values when replayed under HIP's graph packet
+// capture).
+constexpr int kCfgBlocks = 128;  // partials per sample (upper bound; one per lane of a block)
+static_assert(kCfgBlocks <= kBlock, "cfg_partial_sums: one partial per lane");
+
+inline int cfg_blocks(int64_t P) {
+  const int64_t g = vd_cdiv(P, (int64_t)kBlock * 8);
+  return (int)(g < kCfgBlocks ? (g > 0 ? g : 1) : kCfgBlocks);
+}
+inline int64_t cfg_chunk(int64_t P, int nb) { return vd_cdiv(vd_cdiv(P, nb), 8) * 8; }
+
+// The guided noise of n elements, shared by the statistics and by both consumers.
+struct CfgGuide {
+  float w;
+  __device__ __forceinline__ void run(const float* c, const float* u, float f, bool scale,
+                                      float* g, int n) const {
+    for (int i = 0; i < n; ++i) {
+      const float v = fmaf(w, c[i] - u[i], u[i]);
+      g[i] = scale ? f * v : v;
+    }
+  }
+};
+
+// both lanes' values summed by the LDS tree of mse_partial_kernel; the result in red[.][0]
+__device__ __forceinline__ void cfg_block_sum2(float (&red)[2][kBlock], float a, float b) {
+  red[0][threadIdx.x] = a;
+  red[1][threadIdx.x] = b;
+  __syncthreads();
+#pragma unroll
+  for (int w = kBlock / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + w];
+      red[1][threadIdx.x] += red[1][threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+}
+
+// The sample's nb partials of slots `slot` and `slot + 1` summed: lane k takes partial k (one
+// load per lane instead of a serial walk), then the fixed tree.  Ends with a barrier: red is
+// free again.
+__device__ __forceinline__ void cfg_partial_sums(float (&red)[2][kBlock], const float* row,
+                                                 int nb, int slot, float& a, float& b) {
+  float pa = 0.f, pb = 0.f;
+  if ((int)threadIdx.x < nb) {
+    pa = row[threadIdx.x * 4 + slot];
+    pb = row[threadIdx.x * 4 + slot + 1];
+  }
+  cfg_block_sum2(red, pa, pb);
+  a = red[0][0];
+  b = red[1][0];
+  __syncthreads();
+}
+
+// CENTRED = false: slots 0 / 1 = sum c, sum g; true: slots 2 / 3 = centred sums of squares.
+// VEC = 8 needs per_sample % 8 == 0 (then every range is whole 8-vectors) and 16-B alignment.
+template <typename T, int VEC, bool CENTRED>
+__global__ void __launch_bounds__(kBlock) cfg_stats_kernel(const T* __restrict__ c,
+                                                           const T* __restrict__ u, CfgGuide op,
+                                                           int64_t P, int64_t chunk, float* part) {
+  __shared__ float red[2][kBlock];
+  const int nb = gridDim.x;
+  const int64_t b = blockIdx.y;
+  float* row = part + b * nb * 4;
+  float mc = 0.f, mg = 0.f;
+  if (CENTRED) {
+    cfg_partial_sums(red, row, nb, 0, mc, mg);
+    mc /= (float)P;
+    mg /= (float)P;
+  }
+  const int64_t lo = (int64_t)blockIdx.x * chunk;
+  const int64_t hi = lo + chunk < P ? lo + chunk : P;
+  const T* cb = c + b * P;
+  const T* ub = u + b * P;
+  float sc = 0.f, sg = 0.f;
+  for (int64_t i = lo + (int64_t)threadIdx.x * VEC; i < hi; i += (int64_t)kBlock * VEC) {
+    float xc[8], xu[8], g[8];
+    ld_vec(cb + i, xc, VEC);
+    ld_vec(ub + i, xu, VEC);
+    op.run(xc, xu, 1.f, false, g, VEC);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      if (CENTRED) {
+        const float dc = xc[k] - mc, dg = g[k] - mg;
+        sc = fmaf(dc, dc, sc);
+        sg = fmaf(dg, dg, sg);
+      } else {
+        sc += xc[k];
+        sg += g[k];
+      }
+    }
+  }
+  cfg_block_sum2(red, sc, sg);
+  if (threadIdx.x == 0) {
+    row[blockIdx.x * 4 + (CENTRED ? 2 : 0)] = red[0][0];
+    row[blockIdx.x * 4 + (CENTRED ? 3 : 1)] = red[1][0];
+  }
+}
+
+// f_b from the sample's partials, added in the fixed order of cfg_partial_sums: every block of
+// a sample, in either consumer, gets the same bits.  Called by all kBlock threads of a block.
+// A constant guided noise (SS(g) = 0: the all-zero eps of a freshly initialised model, whose
+// output conv is zero) has no std to match; it is left as it is, f_b = 1, where the formula's
+// 0 / 0 would turn the whole sample into NaN.
+__device__ __forceinline__ float cfg_factor(const float* __restrict__ part, int64_t b, int nb,
+                                            float phi) {
+  __shared__ float red[2][kBlock];
+  float qc, qg;
+  cfg_partial_sums(red, part + b * nb * 4, nb, 2, qc, qg);
+  if (qg == 0.f) return 1.f;
+  return phi * sqrtf(qc / qg) + (1.f - phi);
+}
+
+// Guide + rescale + DDIM step in one pass: reads xt, c, u (and z), writes x_prev (twice when
+// xdup is given: the graph sampler's doubled-batch input) and x0.  blockIdx.y = sample, so a
+// block takes f_b once; x_prev may alias xt (a lane reads its elements before it writes them).
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kBlock) cfg_ddim_kernel(
+    DDIMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
+    const T* __restrict__ z, T* xprev, T* xdup, T* __restrict__ x0,
+    const int64_t* __restrict__ t, const float* __restrict__ part, int nb, float phi,
+    int64_t per_sample) {
+  const int64_t b = blockIdx.y;
+  const bool scale = phi > 0.f;
+  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
+  const int64_t tb = t[b], tp = op.tprev[b];
+  const int64_t base = b * per_sample;
+  const int64_t nvec = per_sample / VEC;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = base + v * VEC;
+    float xa[8], xc[8], xu[8], xz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
+    ld_vec(xt + e, xa, VEC);
+    ld_vec(c + e, xc, VEC);
+    ld_vec(u + e, xu, VEC);
+    if (z) ld_vec(z + e, xz, VEC);
+    gd.run(xc, xu, f, scale, g, VEC);
+    op.run(tb, tp, xa, g, xz, y0, y1, VEC);
+    st_vec(xprev + e, y0, VEC);
+    if (xdup) st_vec(xdup + e, y0, VEC);
+    if (x0) st_vec(x0 + e, y1, VEC);
+  }
+}
+
+// The same guided noise written out (the DDPM p_sample_* kernels take it as their eps).
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kBlock) cfg_combine_kernel(
+    CfgGuide gd, const T* __restrict__ c, const T* __restrict__ u, T* __restrict__ out,
+    const float* __restrict__ part, int nb, float phi, int64_t per_sample) {
+  const int64_t b = blockIdx.y;
+  const bool scale = phi > 0.f;
+  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
+  const int64_t base = b * per_sample;
+  const int64_t nvec = per_sample / VEC;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = base + v * VEC;
+    float xc[8], xu[8], g[8];
+    ld_vec(c + e, xc, VEC);
+    ld_vec(u + e, xu, VEC);
+    gd.run(xc, xu, f, scale, g, VEC);
+    st_vec(out + e, g, VEC);
+  }
+}
+
+// 8-wide path: whole vectors per sample and every pointer 16-B aligned
+inline bool cfg_vec8(int64_t per_sample, std::initializer_list<const void*> ptrs) {
+  uintptr_t a = 0;
+  for (const void* p : ptrs) a |= reinterpret_cast<uintptr_t>(p);
+  return per_sample % 8 == 0 && a % 16 == 0;
+}
+
+inline dim3 cfg_grid(int64_t per_sample, int vec, int64_t B) {
+  return dim3((unsigned)grid_for(per_sample / vec), (unsigned)B);
 }
 
 }  // namespace
@@ -727,6 +919,89 @@ int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev, v
     else
       ddim_kernel<T, 1><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
           op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
+  });
+}
+
+size_t vd_cfg_workspace_size(int64_t B, int64_t per_sample) {
+  if (B <= 0 || per_sample <= 0) return 0;
+  return (size_t)B * cfg_blocks(per_sample) * 4 * sizeof(float);
+}
+
+int vd_cfg_stats(const void* eps_c, const void* eps_u, float w, int64_t B, int64_t per_sample,
+                 int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  VD_REQUIRE(eps_c && eps_u && workspace, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
+             (long long)B, (long long)per_sample);
+  VD_REQUIRE(workspace_bytes >= vd_cfg_workspace_size(B, per_sample), "workspace too small");
+  const int nb = cfg_blocks(per_sample);
+  const int64_t chunk = cfg_chunk(per_sample, nb);
+  const dim3 grid((unsigned)nb, (unsigned)B);
+  const CfgGuide gd{w};
+  float* part = static_cast<float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {eps_c, eps_u});
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    const T* c = (const T*)eps_c;
+    const T* u = (const T*)eps_u;
+    if (v8) {
+      cfg_stats_kernel<T, 8, false><<<grid, kBlock, 0, st>>>(c, u, gd, per_sample, chunk, part);
+      cfg_stats_kernel<T, 8, true><<<grid, kBlock, 0, st>>>(c, u, gd, per_sample, chunk, part);
+    } else {
+      cfg_stats_kernel<T, 1, false><<<grid, kBlock, 0, st>>>(c, u, gd, per_sample, chunk, part);
+      cfg_stats_kernel<T, 1, true><<<grid, kBlock, 0, st>>>(c, u, gd, per_sample, chunk, part);
+    }
+  });
+}
+
+int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                     void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                     const int64_t* t_prev, const float* acp, float w, float rescale,
+                     const void* workspace, float eta, int clip, int64_t B, int64_t per_sample,
+                     int dtype, void* stream) {
+  VD_REQUIRE(xt && eps_c && eps_u && x_prev && t && t_prev && acp, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
+             (long long)B, (long long)per_sample);
+  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
+  VD_REQUIRE(rescale == 0.f || workspace, "rescale > 0 needs the vd_cfg_stats workspace (null)");
+  VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
+  DDIMStep op{acp, t_prev, eta, clip, z != nullptr};
+  const CfgGuide gd{w};
+  const int nb = cfg_blocks(per_sample);
+  const float* part = static_cast<const float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0});
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (v8)
+      cfg_ddim_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
+    else
+      cfg_ddim_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
+  });
+}
+
+int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w, float rescale,
+                   const void* workspace, int64_t B, int64_t per_sample, int dtype,
+                   void* stream) {
+  VD_REQUIRE(eps_c && eps_u && eps_out, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
+             (long long)B, (long long)per_sample);
+  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
+  VD_REQUIRE(rescale == 0.f || workspace, "rescale > 0 needs the vd_cfg_stats workspace (null)");
+  const CfgGuide gd{w};
+  const int nb = cfg_blocks(per_sample);
+  const float* part = static_cast<const float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {eps_c, eps_u, eps_out});
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (v8)
+      cfg_combine_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          gd, (const T*)eps_c, (const T*)eps_u, (T*)eps_out, part, nb, rescale, per_sample);
+    else
+      cfg_combine_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          gd, (const T*)eps_c, (const T*)eps_u, (T*)eps_out, part, nb, rescale, per_sample);
   });
 }
 

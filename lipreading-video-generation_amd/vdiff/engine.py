@@ -64,13 +64,24 @@ def reinit_nonzero(model, seed=1234, std=0.02):
     return model
 
 
+def audio_keep_mask(batch, p, device, generator=None):
+    """Per-clip audio keep mask for conditioning dropout: float [batch], 0 with probability p
+    (the clip trains on the null audio), else 1.  Drawn on `device` (the generator's device),
+    no host sync.  p = 0 keeps every clip, p = 1 drops every clip."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"audio_drop_prob {p} outside [0, 1]")
+    u = torch.rand((batch,), generator=generator, device=device)
+    return (u >= p).to(torch.float32)
+
+
 class Trainer:
     """q_sample -> denoiser -> MSE(eps_pred, eps) -> backward -> all-reduce -> Adam.
 
     train.py:102-103: Adam(model.parameters(), lr=1e-2), MSELoss."""
 
     def __init__(self, model, scheduler, lr=1e-2, bucket_mb=25.0, fused_adam=True,
-                 check_every=50, batch_pack=True, graph=False, loss_fn=None):
+                 check_every=50, batch_pack=True, graph=False, loss_fn=None,
+                 audio_drop_prob=0.0, drop_generator=None):
         """check_every: the loss finiteness flag (kept on the device, updated every step) is
         read on the host every `check_every` steps and by check_finite(); a non-finite
         loss raises FloatingPointError naming the first bad step.  0 disables it.
@@ -79,7 +90,15 @@ class Trainer:
         graph: replay the denoiser's forward + backward as one HIP graph (TrainStepGraph);
         one process only.
         loss_fn: (pred, eps) -> scalar loss; default ops.mse_loss (vd_mse_loss, fixed-order).
-        Host-logic tests on CPU pass torch's F.mse_loss (the product ops refuse CPU tensors)."""
+        Host-logic tests on CPU pass torch's F.mse_loss (the product ops refuse CPU tensors).
+        audio_drop_prob: share of the clips that train on the null audio (zero features), the
+        unconditional half of classifier-free guidance; the model must take `audio_keep`
+        (UNetAudio).  0: no mask is drawn and the model is called as before.
+        drop_generator: torch.Generator (on the clips' device) of the keep masks."""
+        if not 0.0 <= audio_drop_prob <= 1.0:
+            raise ValueError(f"audio_drop_prob {audio_drop_prob} outside [0, 1]")
+        self.audio_drop_prob = float(audio_drop_prob)
+        self.drop_generator = drop_generator
         self.model = model
         self.loss_fn = loss_fn or ops.mse_loss
         self.scheduler = scheduler
@@ -113,11 +132,22 @@ class Trainer:
             return self.graph.step(clip)
         return self._eager_step(clip)
 
+    def audio_keep(self, clip: Clip):
+        """This step's keep mask ([B], on the clip's device), or None without dropout."""
+        if self.audio_drop_prob <= 0:
+            return None
+        return audio_keep_mask(clip.x0.shape[0], self.audio_drop_prob, clip.x0.device,
+                               self.drop_generator)
+
     def _eager_step(self, clip: Clip) -> torch.Tensor:
         self.model.train()
+        keep = self.audio_keep(clip)
         with self.packs:
             xt = self.scheduler.add_noise(clip.x0, clip.eps, clip.t)
-            pred = self.model(xt, clip.cond, clip.audio, clip.t)
+            if keep is None:
+                pred = self.model(xt, clip.cond, clip.audio, clip.t)
+            else:
+                pred = self.model(xt, clip.cond, clip.audio, clip.t, audio_keep=keep)
             loss = self.loss_fn(pred, clip.eps)
             loss.backward()
         if self.bucketer is not None:
@@ -211,14 +241,20 @@ class TrainStepGraph:
         model = tr.model
         model.train()
         enc = model.encode_audio(clip.audio).float()
-        if self.g is None:
-            self._capture(clip, enc)
-        elif self._shapes(clip, enc) != self.shapes:
+        if self.g is not None and self._shapes(clip, enc) != self.shapes:
             # a batch of another shape (a short last batch): eager, with every gradient
             # released first so that the eager backward does not accumulate into the graph's
             tr.opt.zero_grad(set_to_none=True)
             self.steps += 1
             return tr._eager_step(clip)
+        keep = tr.audio_keep(clip)
+        if keep is not None:
+            # conditioning dropout, eagerly and before the copy into the static buffer: the
+            # graph sees features, never the mask
+            from .unet_audio import apply_audio_keep
+            enc = apply_audio_keep(enc, keep)
+        if self.g is None:
+            self._capture(clip, enc)
         for p, g in self.grads:  # (an eager step in between may have released them)
             p.grad = g
         with torch.no_grad():
@@ -303,11 +339,25 @@ class TrainStepGraph:
 
 
 @torch.no_grad()
-def sample_ddim(model, sampler, cond, audio, shape, generator=None, callback=None):
+def sample_ddim(model, sampler, cond, audio, shape, generator=None, callback=None,
+                guidance_scale=1.0, guidance_rescale=0.0):
     """DDIM sampling (build extension of test.py:51-83): audio encoded once, packed conv
-    weights reused across steps (ops.frozen_weights)."""
+    weights reused across steps (ops.frozen_weights).
+
+    guidance_scale w != 1: classifier-free audio guidance.  Each step runs one forward at batch
+    2B -- rows [0, B) with the encoded audio, rows [B, 2B) with the null audio (zeros, what
+    Trainer(audio_drop_prob=...) trains on) -- and steps on eps_u + w (eps_c - eps_u),
+    std-rescaled per sample by guidance_rescale (Lin et al. 2023; 0 = off).  w == 1 is the
+    unguided path, unchanged."""
     with ops.frozen_weights():
-        return _sample_ddim(model, sampler, cond, audio, shape, generator, callback)
+        return _sample_ddim(model, sampler, cond, audio, shape, generator, callback,
+                            float(guidance_scale), float(guidance_rescale))
+
+
+def _doubled(cond, feats):
+    """The conditioning of a guided forward at batch 2B: cond repeated, and the encoded audio
+    followed by the null audio (zeros of the same shape)."""
+    return torch.cat([cond, cond]), torch.cat([feats, torch.zeros_like(feats)])
 
 
 class GraphUnsafe(RuntimeError):
@@ -319,16 +369,30 @@ class DDIMGraph:
     as a HIP graph and replayed per step (no per-kernel launch gaps, no host work per
     step).  The sample lives in a static buffer updated in place; the step's timesteps are
     copied device-to-device from the sampler's table before each replay.  Use inside
-    ops.frozen_weights() (the graph reads the cached packed conv weights); eta must be 0."""
+    ops.frozen_weights() (the graph reads the cached packed conv weights); eta must be 0.
 
-    def __init__(self, model, sampler, cond, feats, xt):
+    guidance_scale != 1 (classifier-free audio guidance): the captured step is the UNet forward
+    at batch 2B + vd_cfg_stats (guidance_rescale > 0) + vd_ddim_step_cfg.  The graph owns a
+    static [2B, ...] input whose halves are the fused kernel's x_prev and x_prev_dup, so the
+    doubled input stays current without a copy; the doubled cond / audio / timestep buffers and
+    the null audio are built here, before capture (no memset node in the step)."""
+
+    def __init__(self, model, sampler, cond, feats, xt, guidance_scale=1.0, guidance_rescale=0.0):
         if sampler.eta != 0:
             raise ValueError("DDIMGraph: eta = 0 (deterministic DDIM) only")
         dev = xt.device
         B = xt.shape[0]
         self.model, self.sampler = model, sampler
+        self.scale, self.rescale = float(guidance_scale), float(guidance_rescale)
+        self.guided = self.scale != 1.0
+        if self.guided:
+            cond, feats = _doubled(cond, feats)
+            self.x2 = torch.cat([xt, xt])
+            self.xt, self.xdup = self.x2[:B], self.x2[B:]
+            B = 2 * B  # rows of the timestep buffers (the step kernel reads the first half)
+        else:
+            self.xt = xt.clone()
         self.cond, self.feats = cond, feats
-        self.xt = xt.clone()
         self.t_all = sampler.timesteps.to(dev).view(-1, 1).expand(-1, B).contiguous()
         self.tp_all = sampler.prev_timesteps.to(dev).view(-1, 1).expand(-1, B).contiguous()
         self.t = self.t_all[0].clone()
@@ -338,6 +402,14 @@ class DDIMGraph:
         self.x0 = None
 
     def _body(self):
+        if self.guided:
+            B = self.xt.shape[0]
+            eps = self.model(self.x2, self.cond, self.feats, self.t)
+            eps_c, eps_u = eps.to(self.xt.dtype).chunk(2)
+            _, x0 = ops.ddim_step_cfg(self.xt, eps_c, eps_u, self.t[:B], self.tp[:B], self.acp,
+                                      self.scale, self.rescale, clip=self.sampler.clip_x0,
+                                      out=self.xt, dup=self.xdup)
+            return x0
         eps = self.model(self.xt, self.cond, self.feats, self.t)
         xp, x0 = ops.ddim_step(self.xt, eps.to(self.xt.dtype), self.t, self.tp, self.acp,
                                eta=0.0, clip=self.sampler.clip_x0)
@@ -351,9 +423,10 @@ class DDIMGraph:
         side = torch.cuda.Stream(device=self.xt.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):  # eager warm-up: packed weights, tables, workspaces
-            keep = self.xt.clone()
+            buf = self.x2 if self.guided else self.xt
+            keep = buf.clone()
             self._body()
-            self.xt.copy_(keep)
+            buf.copy_(keep)
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True)  # node list kept (node_types)
         with hipgraph.capture(self.graph):
@@ -385,14 +458,15 @@ def _use_graph(device, sampler):
             and os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0")
 
 
-def _sample_ddim(model, sampler, cond, audio, shape, generator, callback):
+def _sample_ddim(model, sampler, cond, audio, shape, generator, callback, scale=1.0,
+                 rescale=0.0):
     model.eval()
     device = cond.device
     feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
     xt = torch.randn(shape, generator=generator, device=device)
     x0 = None
     if _use_graph(device, sampler):
-        g = DDIMGraph(model, sampler, cond, feats, xt)
+        g = DDIMGraph(model, sampler, cond, feats, xt, scale, rescale)
         try:
             g.capture()
         except GraphUnsafe as e:
@@ -404,10 +478,17 @@ def _sample_ddim(model, sampler, cond, audio, shape, generator, callback):
                 if callback is not None:  # the graph's static buffers: the next replay rewrites them
                     callback(i, xt.clone(), x0.clone())
             return xt.clone(), x0.clone()
+    guided = scale != 1.0
+    if guided:
+        cond, feats = _doubled(cond, feats)
+    nb = (2 if guided else 1) * shape[0]
     for i in range(sampler.steps):
-        t = torch.full((shape[0],), int(sampler.timesteps[i]), dtype=torch.int64, device=device)
-        eps = model(xt, cond, feats, t)
-        xt, x0 = sampler.step(xt, eps, i)
+        t = torch.full((nb,), int(sampler.timesteps[i]), dtype=torch.int64, device=device)
+        if guided:
+            eps_c, eps_u = model(torch.cat([xt, xt]), cond, feats, t).chunk(2)
+            xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale)
+        else:
+            xt, x0 = sampler.step(xt, model(xt, cond, feats, t), i)
         if callback is not None:
             callback(i, xt, x0)
     return xt, x0
@@ -415,23 +496,32 @@ def _sample_ddim(model, sampler, cond, audio, shape, generator, callback):
 
 @torch.no_grad()
 def sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps=None, generator=None,
-                callback=None):
-    """Ancestral sampling as test.py:51-83 (V2 scheduler by default there)."""
+                callback=None, guidance_scale=1.0, guidance_rescale=0.0):
+    """Ancestral sampling as test.py:51-83 (V2 scheduler by default there).  guidance_scale !=
+    1: classifier-free audio guidance as in sample_ddim; the guided noise (ops.cfg_combine) is
+    the eps of the scheduler's p_sample kernel."""
     with ops.frozen_weights():
         return _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator,
-                            callback)
+                            callback, float(guidance_scale), float(guidance_rescale))
 
 
-def _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator, callback):
+def _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator, callback,
+                 scale=1.0, rescale=0.0):
     model.eval()
     device = cond.device
     feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
     n = n_timesteps or scheduler.num_timesteps
     xt = torch.randn(shape, generator=generator, device=device)
     x0 = None
+    if scale != 1.0:
+        cond2, feats2 = _doubled(cond, feats)
     for i in reversed(range(n)):
         t = torch.full((shape[0],), i, dtype=torch.int64, device=device)
-        eps = model(xt, cond, feats, t)
+        if scale != 1.0:
+            eps_c, eps_u = model(torch.cat([xt, xt]), cond2, feats2, torch.cat([t, t])).chunk(2)
+            eps = ops.cfg_combine(eps_c, eps_u, scale, rescale)
+        else:
+            eps = model(xt, cond, feats, t)
         z = torch.randn(xt.shape, generator=generator, device=device)
         xt, x0 = scheduler.sample_prev_timestep(xt, eps, t, z=z)
         if callback is not None:

@@ -135,3 +135,15 @@ class DDIMSampler:
             z = torch.randn_like(xt)
         return ops.ddim_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), t, tp,
                              self._acp(xt.device), eta=self.eta, z=z, clip=self.clip_x0)
+
+    def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, z=None):
+        """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
+        by `rescale`: guide, rescale and update in one kernel (ops.ddim_step_cfg)."""
+        B = xt.shape[0]
+        t = torch.full((B,), int(self.timesteps[i]), dtype=torch.int64, device=xt.device)
+        tp = torch.full((B,), int(self.prev_timesteps[i]), dtype=torch.int64, device=xt.device)
+        if self.eta > 0 and z is None:
+            z = torch.randn_like(xt)
+        return ops.ddim_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
+                                 eps_u.contiguous().to(xt.dtype), t, tp, self._acp(xt.device),
+                                 scale, rescale, eta=self.eta, z=z, clip=self.clip_x0)

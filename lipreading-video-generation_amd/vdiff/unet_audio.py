@@ -147,6 +147,17 @@ class AudioFeatureTransformer(nn.Module):
         return self.transform(x)
 
 
+def apply_audio_keep(enc, keep):
+    """Encoded audio ([B*T, F] features or [B*T, L, F] tokens) with the T windows of every clip
+    whose keep[b] is 0 multiplied by 0, before audio_transformer and before the cross-attention
+    context (no host sync: the mask stays on the device)."""
+    B = keep.shape[0]
+    if enc.shape[0] % B:
+        raise ValueError(f"audio_keep has {B} entries for {enc.shape[0]} audio windows")
+    k = keep.to(enc.dtype).repeat_interleave(enc.shape[0] // B)
+    return enc * k.view(-1, *([1] * (enc.dim() - 1)))
+
+
 class UNetAudio(UNetModel):
     """unet_audio.py:32-66, same constructor arguments (plus keyword-only
     extensions of UNetModel and `audio_encoder_pretrained` / `freeze_audio_encoder`)."""
@@ -203,10 +214,15 @@ class UNetAudio(UNetModel):
             tokens = self.audio_encoder(audio)
         return tokens if self.audio_attention else tokens.mean(dim=1)
 
-    def forward(self, image, cond_image, audio, timesteps, y=None):
+    def forward(self, image, cond_image, audio, timesteps, y=None, audio_keep=None):
+        """audio_keep ([B], 1 = keep, 0 = drop; None = keep all): conditioning dropout for
+        classifier-free guidance.  A dropped clip's T windows get the null audio -- zero
+        features / tokens -- which is what the guided samplers feed their unconditional half."""
         B = image.shape[0]
         T = image.shape[2] if image.dim() == 5 else 1
         enc = self.encode_audio(audio).float()
+        if audio_keep is not None:
+            enc = apply_audio_keep(enc, audio_keep)
         tokens = enc if enc.dim() == 3 else None
         if self.audio_attention and tokens is None:
             raise ValueError("audio_attention needs the audio tokens [B*T, L, F], not pooled "

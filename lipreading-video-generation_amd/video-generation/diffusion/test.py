@@ -1,6 +1,7 @@
 """Sampling entry point (drop-in for video-generation/diffusion/test.py) on MI355X.
 
     python test.py [--ckpt model.pth | --random-init] [--sampler ddpm-v2|ddim] [--steps 500]
+                   [--guidance-scale 1.0] [--guidance-rescale 0.0]
 
 Reference API kept (importable without running anything, unlike the reference script):
   * `config` -- the dict of test.py:33-49 (same keys; `ldm_params` may also carry the
@@ -31,7 +32,7 @@ import torch
 
 import _vdiff_path  # noqa: F401
 from vdiff.engine import reinit_nonzero, sample_ddim, synthetic_clip
-from vdiff.ops import frozen_weights
+from vdiff.ops import cfg_combine, frozen_weights
 
 from linear_noise_scheduler import LinearNoiseSchedulerV2
 from noise_scheduler import DDIMSampler
@@ -115,14 +116,18 @@ def _frames_of(model, audio_cond):
 
 @torch.no_grad()
 def sample_images(model, scheduler, img_cond, audio_cond, n_timesteps=500, *, out_dir=OUT_DIR,
-                  save_every=50, generator=None, noise=None, max_steps=None, callback=None):
+                  save_every=50, generator=None, noise=None, max_steps=None, callback=None,
+                  guidance_scale=1.0, guidance_rescale=0.0):
     """test.py:51-83: reverse process i = n_timesteps-1 .. 0 with
     scheduler.sample_prev_timestep (LinearNoiseSchedulerV2 in test.py), x0 saved every
     `save_every` steps and at i == 0; returns the final x0.
 
     Keyword-only extensions: `noise(shape)` supplies x_T and each step's z instead of
     torch.randn (injected noise: the trajectory parity tests); `max_steps` stops after that
-    many steps; `callback(i, xt, x0)` sees every step's output."""
+    many steps; `callback(i, xt, x0)` sees every step's output; `guidance_scale` != 1 samples
+    with classifier-free audio guidance (one forward at batch 2, the second row with the null
+    audio; `guidance_rescale` is the std-rescale of Lin et al. 2023), for a model trained with
+    train.py --audio-drop-prob."""
     model.eval()
     dev = img_cond.device
     S = config["dataset_params"]["im_size"]
@@ -133,12 +138,21 @@ def sample_images(model, scheduler, img_cond, audio_cond, n_timesteps=500, *, ou
     feats = model.encode_audio(audio_cond)  # once per clip (the reference: every step)
     xt = draw(shape).to(dev)
     x0 = None
+    guided = float(guidance_scale) != 1.0
+    if guided:
+        cond2 = torch.cat([img_cond, img_cond])
+        feats2 = torch.cat([feats, torch.zeros_like(feats)])
     with frozen_weights():  # packed conv weights reused across the steps
         for k, i in enumerate(reversed(range(n_timesteps))):
             if max_steps is not None and k == max_steps:
                 break
             t = torch.tensor([i], dtype=torch.long, device=dev)
-            eps = model(xt, img_cond, feats, t)
+            if guided:
+                eps_c, eps_u = model(torch.cat([xt, xt]), cond2, feats2,
+                                     torch.cat([t, t])).chunk(2)
+                eps = cfg_combine(eps_c, eps_u, guidance_scale, guidance_rescale)
+            else:
+                eps = model(xt, img_cond, feats, t)
             z = draw(xt.shape).to(dev)
             xt, x0 = scheduler.sample_prev_timestep(xt, eps, t, z=z)
             if callback is not None:
@@ -167,6 +181,11 @@ def parse(argv=None):
     ap.add_argument("--cond-npz", default=None)
     ap.add_argument("--save-every", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--guidance-scale", type=float, default=1.0,
+                    help="classifier-free audio guidance weight (1 = off; needs a model trained "
+                         "with --audio-drop-prob)")
+    ap.add_argument("--guidance-rescale", type=float, default=0.0,
+                    help="std-rescale of the guided noise in [0, 1] (Lin et al. 2023)")
     return ap.parse_args(argv)
 
 
@@ -207,11 +226,15 @@ def main(argv=None):
             if (i + 1) % args.save_every == 0 or i == sampler.steps - 1:
                 save_frame(x0, os.path.join(args.out_dir, f"x0_{i}"))
 
-        _, x0 = sample_ddim(model, sampler, cond, audio, shape, generator=g, callback=cb)
+        _, x0 = sample_ddim(model, sampler, cond, audio, shape, generator=g, callback=cb,
+                            guidance_scale=args.guidance_scale,
+                            guidance_rescale=args.guidance_rescale)
         print("All images have been processed and saved.")
         return x0
     return sample_images(model, scheduler, cond, audio, n_timesteps=args.steps or 500,
-                         out_dir=args.out_dir, save_every=args.save_every, generator=g)
+                         out_dir=args.out_dir, save_every=args.save_every, generator=g,
+                         guidance_scale=args.guidance_scale,
+                         guidance_rescale=args.guidance_rescale)
 
 
 if __name__ == "__main__":

@@ -66,6 +66,9 @@ def parse(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--random-audio-encoder", action="store_true",
                     help="random-init wav2vec2-base when its pretrained weights are absent")
+    ap.add_argument("--audio-drop-prob", type=float, default=0.0,
+                    help="share of the clips trained on the null audio (0.1-0.2 for a model "
+                         "sampled with test.py --guidance-scale; build extension)")
     ap.add_argument("--reinit-nonzero", action="store_true",
                     help="seeded weights for the zero-initialised layers (smoke / bench only)")
     return ap.parse_args(argv)
@@ -102,7 +105,11 @@ def train(argv=None):
         reinit_nonzero(model, seed=args.seed)
     model = model.to(device)
     broadcast_parameters(model)
-    trainer = Trainer(model, scheduler, lr=args.lr)
+    drop_gen = None
+    if args.audio_drop_prob > 0:  # the keep masks: a seeded stream of their own per rank
+        drop_gen = torch.Generator(device=device).manual_seed(args.seed * 7919 + rank)
+    trainer = Trainer(model, scheduler, lr=args.lr, audio_drop_prob=args.audio_drop_prob,
+                      drop_generator=drop_gen)
     start_epoch = 0
     if args.resume:
         state = torch.load(args.resume, map_location=device, weights_only=True)
