@@ -9,6 +9,8 @@ module provides
   * `Stream` -- an instruction list that tracks the wait-state hazards gfx950 does not
     interlock and pads them with s_nop, and derives the counted lgkmcnt waits of every
     consumer of an LDS read;
+  * the pieces every kernel's generator shares (tile swizzle and lane-table entries, prologue
+    sequences, LDS-DMA issue, the cost-driven VALU gap scheduler `place`);
   * `kernel_text` -- the code object wrapper (.amdhsa_kernel descriptor + metadata).
 
 Hazard distances (gfx950; measured from hipcc's own padding of the same instruction pairs, the
@@ -233,35 +235,217 @@ class Stream:
         return "\n".join(self.lines) + "\n"
 
 
+# ------------------------------------------------------------------ shared kernel pieces
+# Plain functions over a Stream and register names.  Each emits the same instruction
+# sequence for every kernel that uses it; the generators keep only what is theirs (register
+# plan, SGPR map, MFMA order, VALU lists, slot tables).
+HI = 65536             # ds_read immediates are 16 bits: offsets >= 64 KiB use +64 KiB bases
+COST = {"exp": 8.0, "add": 4.0, "cvt": 4.5, "cmp": 4.0, "cnd": 4.0}   # VALU issue cycles
+
+
+def _first(rng: str) -> int:
+    """First register number of 's[60:63]' / 's60'."""
+    return int(rng.strip("s[]").split(":")[0])
+
+
+def swz(d, r):
+    """attention.hip swz_row<d>: the 16-B chunk XOR of row r of a bf16 tile with d-element rows
+    (d = 64, or 128 / 256 which share one rule)."""
+    if d == 64:
+        return (((r >> 1) & 1) << 2) | ((r >> 2) & 3)
+    return ((r & 3) << 2) | ((r >> 2) & 3)
+
+
+def toff_bytes(d, r, c):
+    """attention.hip toff<bf16, d>(r, c) in bytes."""
+    return 2 * (r * d + (((c >> 3) ^ swz(d, r)) << 3) + (c & 7))
+
+
+def frag_offsets(d, lane, nrow, ntr):
+    """A lane's table entries for a bf16 tile with d-element rows: the nrow row-fragment
+    offsets (attention.hip mma_rows: k-step s, block row 0), then the 2 ntr transposed-fragment
+    offsets (mma_tr: 2 i + hi, column block i, rows +8 hi; col0 = 32 i, sum0 = 0, s2 = 0)."""
+    r, hh = lane & 31, lane >> 5
+    out = [toff_bytes(d, r, 16 * s + 8 * hh) for s in range(nrow)]
+    g, fr = lane >> 4, lane & 15
+    q4, p4 = fr >> 2, fr & 3
+    for i in range(ntr):
+        col = 32 * i + 16 * (g & 1) + 4 * p4
+        kr = 4 * (g >> 1) + q4
+        out += [toff_bytes(d, kr, col), toff_bytes(d, kr + 8, col)]
+    return out
+
+
+def lds(V, name, k, off):
+    """(base register, immediate) of LDS byte offset `off` from per-lane table entry k of
+    `name` ('rowoff' / 'troff'; their +64 KiB copies are 'rowhi' / 'trhi')."""
+    if off >= HI:
+        return V.r({"rowoff": "rowhi", "troff": "trhi"}[name], k), off - HI
+    return V.r(name, k), off
+
+
+def lane_table_data(symbol, rows):
+    """The .rodata text of a per-lane u32 table."""
+    data = f"\n.rodata\n.p2align 8\n{symbol}:\n"
+    for row in rows:
+        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
+    return data
+
+
+def wave_id(st, V, s_wave):
+    """lane = tid & 63 ; s_wave = the wave's index in the workgroup."""
+    st.emit(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
+    st.raw(f"v_readfirstlane_b32 {s_wave}, {V.r('tid')}")  # first lane's id = 64 * wave
+    st.raw("s_nop 1")
+    st.raw(f"s_lshr_b32 {s_wave}, {s_wave}, 6")
+
+
+def table_addr(st, s_tab, symbol):
+    """s_tab (an aligned pair) = the address of the lane table `symbol`."""
+    lo = _first(s_tab)
+    st.raw(f"s_getpc_b64 s[{lo}:{lo + 1}]")
+    st.raw(f"s_add_u32 s{lo}, s{lo}, {symbol}@rel32@lo+4")
+    st.raw(f"s_addc_u32 s{lo + 1}, s{lo + 1}, {symbol}@rel32@hi+12")
+
+
+def wave_and_table(st, V, s_wave, s_tab, symbol):
+    wave_id(st, V, s_wave)
+    table_addr(st, s_tab, symbol)
+
+
+def rare_targets(st, s_tgt, prefix):
+    """s[s_tgt + 2 v : +1] = the rare-path entry point .L{prefix}_rare{v}, v = 0..3."""
+    st.raw(f"s_getpc_b64 s[{s_tgt}:{s_tgt + 1}]")
+    st.label(f".L{prefix}_pc")
+    for v in (3, 2, 1, 0):
+        st.raw(f"s_add_u32 s{s_tgt + 2 * v}, s{s_tgt}, .L{prefix}_rare{v}-.L{prefix}_pc")
+        st.raw(f"s_addc_u32 s{s_tgt + 2 * v + 1}, s{s_tgt + 1}, 0")
+
+
+def mad64(st, dlo, dhi, a, blo, bhi, t):
+    """dhi:dlo = a * bhi:blo (low 64 bits); t is scratch."""
+    st.raw(f"s_mul_i32 {dlo}, {a}, {blo}")
+    st.raw(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
+    st.raw(f"s_mul_i32 {t}, {a}, {bhi}")
+    st.raw(f"s_add_u32 {dhi}, {dhi}, {t}")
+
+
+def add64(st, dlo, dhi, alo, ahi):
+    """dhi:dlo += ahi:alo."""
+    st.raw(f"s_add_u32 {dlo}, {dlo}, {alo}")
+    st.raw(f"s_addc_u32 {dhi}, {dhi}, {ahi}")
+
+
+def rsrc(st, dst, plo, phi, nrec, base):
+    """Buffer resource dst (4 SGPRs) over nrec bytes from pointer phi:plo + base (a (lo, hi)
+    SGPR pair): 48-bit address, stride 0, raw dword format (0x20000)."""
+    d0 = _first(dst)
+    st.raw(f"s_add_u32 s{d0}, {plo}, {base[0]}")
+    st.raw(f"s_addc_u32 s{d0 + 1}, {phi}, {base[1]}")
+    st.raw(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
+    st.raw(f"s_mov_b32 s{d0 + 2}, {nrec}")
+    st.raw(f"s_mov_b32 s{d0 + 3}, 0x20000")
+
+
+def scale_bf16(st, v0, n, s_scale, t0, t1, dst):
+    """v[v0 .. v0 + n) *= s_scale per bf16 element (attention.hip RowFrag::scale), each word
+    then copied to the AGPR dst(w)."""
+    e = st.emit
+    for w in range(n):
+        x = f"v{v0 + w}"
+        e(f"v_lshlrev_b32 {t0}, 16, {x}")
+        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
+        e(f"v_mul_f32 {t0}, {s_scale}, {t0}")
+        e(f"v_mul_f32 {t1}, {s_scale}, {t1}")
+        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
+        e(f"v_accvgpr_write_b32 {dst(w)}, {x}")
+
+
+def dma_issue(st, ops, adv=()):
+    """LDS-DMA pieces ops = [(M0 setup, buffer_load ... lds)], then the source-offset
+    advances adv (after a tile's last piece)."""
+    for m0, ld in ops:
+        st.raw(m0)
+        st.raw("s_nop 0")
+        st.emit(ld)
+    for a in adv:
+        st.emit(a)
+
+
+def dma_at_gap(st, g, gaps, ops, adv):
+    """Inside a body: the piece whose gap is g (gaps[i] holds ops[i]), if any; the last one is
+    followed by adv."""
+    if g in gaps:
+        i = gaps.index(g)
+        dma_issue(st, ops[i:i + 1], adv if i == len(gaps) - 1 else ())
+
+
+def loop_tail(st, s_iter, label):
+    st.raw(f"s_sub_u32 {s_iter}, {s_iter}, 1")
+    st.raw(f"s_cmp_lg_u32 {s_iter}, 0")
+    st.raw(f"s_cbranch_scc1 {label}")
+
+
+def combine_list(V, chains):
+    """The `chains` row-sum accumulators of each query block into ps (a pairwise tree), as
+    softmax items (text, cost, earliest gap)."""
+    out = []
+    if chains == 1:
+        return [(f"v_mov_b32 {V.r('ps', j)}, {V.r('c', 4 * j)}", COST["add"], 0)
+                for j in range(2)]
+    step = 1
+    while step < chains:
+        last = 2 * step >= chains
+        for a in range(0, chains, 2 * step):
+            for j in range(2):
+                dst = V.r("ps", j) if last else V.r("c", 4 * j + a)
+                out.append((f"v_add_f32 {dst}, {V.r('c', 4 * j + a)}, "
+                            f"{V.r('c', 4 * j + a + step)}", COST["add"], 0))
+        step *= 2
+    return out
+
+
+def place(items, ngaps):
+    """Greedy list schedule of VALU items (text, cost) or (text, cost, earliest gap; default 0)
+    over ngaps MFMA gaps: gap g takes, in list order, the items whose earliest gap has come,
+    until the gap's share of the total cost is used; an item held back by its earliest gap
+    lets the later ones pass (only P^T writes are held back); the last gap takes the rest."""
+    per = sum(it[1] for it in items) / ngaps
+    slots = [[] for _ in range(ngaps)]
+    done = [False] * len(items)
+    budget = 0.0
+    for g in range(ngaps):
+        budget += per
+        last = g == ngaps - 1
+        for k, it in enumerate(items):
+            if done[k] or (len(it) > 2 and it[2] > g):
+                continue
+            if not last and it[1] > budget + 1e-9:
+                break
+            slots[g].append(it[0])
+            budget -= it[1]
+            done[k] = True
+    assert all(done)
+    return slots
+
+
 # Code placement (MI355X_MICROARCH.md "Two waves per SIMD" item 8: a hand-written stream can
-# lose ~13 % under a uniform 4-byte shift): kernels named here start with one s_nop 0, which
-# shifts their whole instruction stream by 4 bytes.  PHASE_FLIP (A/B builds only:
-# gen_attn_asm.py --phase=..., tools/build_asm_phase.sh): "all", or a comma list of kernel
-# names, flips the phase of those kernels relative to this table.  The product build (make)
-# never sets it, and nothing here reads the environment, so a leftover variable cannot
-# shift the shipped code (advisor r04).
-PHASE4 = set()
-PHASE_FLIP = ""
-
-
-def _phase4(name):
-    flip = PHASE_FLIP == "all" or name in PHASE_FLIP.split(",")
-    return (name in PHASE4) != flip
-
-
+# lose ~13 % under a uniform 4-byte shift).  Measured and removed: a per-kernel 4-byte phase
+# shift (one leading s_nop 0) left all nine kernels within +-0.5 %
+# (profiles/r04aj_ab_code_placement.txt, DESIGN_HISTORY.md "Code placement").  Nothing here
+# reads the environment, so a leftover variable cannot shift the shipped code.
 def kernel_text(name, body, *, vgprs, agprs, sgprs, lds_bytes, kernarg_bytes, wg_size,
                 wg_ids=(1, 1, 1)):
     """(code + descriptor text, metadata entry) of one kernel (code object v5)."""
     accum = (vgprs + 3) // 4 * 4
     total = accum + agprs
     assert total <= 512, total
-    pad = "\ts_nop 0\n" if _phase4(name) else ""
     code = f""".text
 .globl {name}
 .p2align 8
 .type {name},@function
 {name}:
-{pad}{body}
+{body}
 \ts_endpgm
 .Lfunc_end_{name}:
 .size {name}, .Lfunc_end_{name}-{name}

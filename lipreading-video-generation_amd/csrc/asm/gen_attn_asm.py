@@ -30,7 +30,15 @@ from __future__ import annotations
 
 import sys
 
-from asmgen import Regs, Stream, code_object_text, kernel_text
+from asmgen import (Regs, Stream, add64, code_object_text, dma_at_gap, dma_issue, frag_offsets,
+                    kernel_text, lane_table_data, loop_tail, mad64, rsrc, scale_bf16, swz,
+                    wave_and_table)
+from gen_d128 import gen_dkdv128, gen_dq128
+from gen_d256 import gen_dq256
+from gen_d256dk import gen_dkdv256
+from gen_fwd import gen_fwd
+from gen_fwd128 import gen_fwd128
+from gen_fwd256 import gen_fwd256
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4            # waves per workgroup
@@ -41,16 +49,6 @@ START = 18        # first VALU gap of a tile's score blocks (after MFMA START)
 
 
 # ------------------------------------------------------------------ lane tables
-def swz(r):
-    """attention.hip swz_row<64>."""
-    return (((r >> 1) & 1) << 2) | ((r >> 2) & 3)
-
-
-def toff_bytes(r, c):
-    """attention.hip toff<bf16, 64>(r, c) in bytes."""
-    return 2 * (r * 64 + (((c >> 3) ^ swz(r)) << 3) + (c & 7))
-
-
 def lane_table():
     """tab[wave][lane][16] u32: 0-3 mma_rows offsets (s = 0..3, block row 0), 4-7 mma_tr
     offsets (i * 2 + hi; col0 = 32 i, sum0 = 0, s2 = 0), 8-9 DMA row in the tile and 10-11
@@ -58,22 +56,13 @@ def lane_table():
     out = []
     for w in range(NW):
         for lane in range(64):
-            r, hh = lane & 31, lane >> 5
-            row = [toff_bytes(r, 16 * s + 8 * hh) for s in range(4)]
-            g, fr = lane >> 4, lane & 15
-            q4, p4 = fr >> 2, fr & 3
-            tr = []
-            for i in range(2):
-                col = 32 * i + 16 * (g & 1) + 4 * p4
-                kr = 4 * (g >> 1) + q4
-                tr += [toff_bytes(kr, col), toff_bytes(kr + 8, col)]
             dma_row, dma_c = [], []
             for i in range(2):
                 gi = w * 2 + i
                 rr = gi * 8 + lane // 8
                 dma_row.append(rr)
-                dma_c.append(((lane % 8) ^ swz(rr)) * 16)
-            out.append(row + tr + dma_row + dma_c + [0, 0, 0, 0])
+                dma_c.append(((lane % 8) ^ swz(64, rr)) * 16)
+            out.append(frag_offsets(64, lane, 4, 2) + dma_row + dma_c + [0, 0, 0, 0])
     return out
 
 
@@ -130,53 +119,29 @@ def prologue_dq(st: Stream, V, A):
     e, r = st.emit, st.raw
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")  # first lane's id = 64 * wave
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
-    r("s_getpc_b64 s[88:89]")
-    r("s_add_u32 s88, s88, vd_attn_dq_lanes@rel32@lo+4")
-    r("s_addc_u32 s89, s89, vd_attn_dq_lanes@rel32@hi+12")
+    wave_and_table(st, V, S_WAVE, S_TAB, "vd_attn_dq_lanes")
     r("s_waitcnt lgkmcnt(0)")
     # seq = wgz * groups + wgy ; base = wgz * bs + wgy * gs ; obase likewise (bytes, 64-bit)
     r(f"s_mul_i32 s48, {S_WGZ}, s33")
     r(f"s_add_u32 s48, s48, {S_WGY}")
-
-    def mad64(dlo, dhi, a, blo, bhi, t):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {t}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {t}")
-
-    mad64("s50", "s51", S_WGZ, "s34", "s35", "s90")
-    mad64("s92", "s93", S_WGY, "s36", "s37", "s90")
-    r("s_add_u32 s50, s50, s92")
-    r("s_addc_u32 s51, s51, s93")
-    mad64("s52", "s53", S_WGZ, "s38", "s39", "s90")
-    mad64("s92", "s93", S_WGY, "s40", "s41", "s90")
-    r("s_add_u32 s52, s52, s92")
-    r("s_addc_u32 s53, s53, s93")
-
-    def rsrc(dst, plo, phi, blo, bhi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {blo}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {bhi}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
-    rsrc(RQ, "s16", "s17", "s50", "s51", "s44")
-    rsrc(RK, "s18", "s19", "s50", "s51", "s44")
-    rsrc(RV, "s20", "s21", "s50", "s51", "s44")
-    rsrc(RO, "s22", "s23", "s52", "s53", "s45")
-    rsrc(RDQ, "s28", "s29", "s50", "s51", "s44")
+    mad64(st, "s50", "s51", S_WGZ, "s34", "s35", "s90")
+    mad64(st, "s92", "s93", S_WGY, "s36", "s37", "s90")
+    add64(st, "s50", "s51", "s92", "s93")
+    mad64(st, "s52", "s53", S_WGZ, "s38", "s39", "s90")
+    mad64(st, "s92", "s93", S_WGY, "s40", "s41", "s90")
+    add64(st, "s52", "s53", "s92", "s93")
+    rsrc(st, RQ, "s16", "s17", "s44", ("s50", "s51"))
+    rsrc(st, RK, "s18", "s19", "s44", ("s50", "s51"))
+    rsrc(st, RV, "s20", "s21", "s44", ("s50", "s51"))
+    rsrc(st, RO, "s22", "s23", "s45", ("s52", "s53"))
+    rsrc(st, RDQ, "s28", "s29", "s44", ("s50", "s51"))
     # row constants: seq * n * 4 bytes into nlse2 / ndelta
     r("s_mul_i32 s92, s48, s30")
     r("s_mul_hi_u32 s93, s48, s30")
     r("s_lshl_b64 s[92:93], s[92:93], 2")
     r("s_lshl_b32 s94, s30, 2")
-    rsrc(RL, "s24", "s25", "s92", "s93", "s94")
-    rsrc(RD, "s26", "s27", "s92", "s93", "s94")
+    rsrc(st, RL, "s24", "s25", "s94", ("s92", "s93"))
+    rsrc(st, RD, "s26", "s27", "s94", ("s92", "s93"))
     # q0 = wgx * 256 + wave * 64 ; M0 base of this wave's DMA pieces = wave * 2048
     r(f"s_lshl_b32 {S_Q0}, {S_WGX}, 8")
     r(f"s_lshl_b32 s90, {S_WAVE}, 6")
@@ -184,7 +149,7 @@ def prologue_dq(st: Stream, V, A):
     r(f"s_lshl_b32 {S_M0}, {S_WAVE}, 11")
     r(f"s_mov_b32 {S_ITER}, s47")
     # lane table: tid * 64 bytes
-    t0, t1, t2, t3 = (V.r("tmp", i) for i in range(4))
+    t0, t1 = V.r("tmp", 0), V.r("tmp", 1)
     e(f"v_lshlrev_b32 {t0}, 6, {V.r('tid')}")
     r(f"global_load_dwordx4 {V.r('rowoff', 0, 4)}, {t0}, {S_TAB}")
     r(f"global_load_dwordx4 {V.r('troff', 0, 4)}, {t0}, {S_TAB} offset:16")
@@ -223,14 +188,7 @@ def prologue_dq(st: Stream, V, A):
         e(f"v_add_u32 {V.r('stq', j)}, {V.r('stq', j)}, {V.r('dpacc', 54)}")
     r("s_waitcnt vmcnt(0)")
     # Q' = bf16(Q * scale * log2 e), per bf16 element (attention.hip RowFrag::scale)
-    for w in range(32):
-        x = f"v{qv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s43, {t0}")
-        e(f"v_mul_f32 {t1}, s43, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('qf', w)}, {x}")
+    scale_bf16(st, qv, 32, "s43", t0, t1, lambda w: A.r("qf", w))
     # srcC splats: il[j] = -lse' (nlse2), id[j] = -delta (ndelta)
     for j in range(2):
         for k in range(16):
@@ -260,19 +218,20 @@ def prologue_dq(st: Stream, V, A):
     r("s_waitcnt lgkmcnt(0)")
     # ring fill: tiles 0 and 1
     for t in range(2):
-        dma_issue(st, V, t)
+        dma_issue(st, *dma_ops(V, t))
 
 
-def dma_issue(st: Stream, V, stage):
-    """The wave's 4 LDS-DMA pieces of the next tile into `stage`, then advance the offsets."""
+def dma_ops(V, stage):
+    """The wave's 4 LDS-DMA pieces of a tile into `stage` (K pieces 0, 1, V pieces 0, 1) and
+    the source-offset advances."""
     d0 = V["dma"]
+    ops = []
     for x, rs in ((0, RK), (1, RV)):
         for i in range(2):
-            st.raw(f"s_add_u32 m0, {S_M0}, {stage * STAGE + x * VOFF + i * 1024}")
-            st.raw("s_nop 0")
-            st.emit(f"buffer_load_dwordx4 v{d0 + i}, {rs}, 0 offen lds")
-    for i in range(2):
-        st.emit(f"v_add_u32 v{d0 + i}, s46, v{d0 + i}")
+            ops.append((f"s_add_u32 m0, {S_M0}, {stage * STAGE + x * VOFF + i * 1024}",
+                        f"buffer_load_dwordx4 v{d0 + i}, {rs}, 0 offen lds"))
+    adv = [f"v_add_u32 v{d0 + i}, s46, v{d0 + i}" for i in range(2)]
+    return ops, adv
 
 
 # ------------------------------------------------------------------ the tile body
@@ -327,7 +286,6 @@ def tile_mfmas(V, A, stage):
 
 def tile_reads(V, A, stage):
     """slot -> [(ds_read text, id)]: slot g is issued before MFMA g."""
-    prev = (stage + 3) % 4
     reads = {}
 
     def add(slot, text, rid):
@@ -354,7 +312,6 @@ def tile_reads(V, A, stage):
                             f"{V.r('troff', 2 * i + hi)} offset:{stage * STAGE + kb * 4096 + s2 * 2048}")
                     add(slot0 + k // 2, text, ("T", kb, i, s2, hi))
                     k += 1
-    del prev
     return reads
 
 
@@ -370,18 +327,9 @@ def emit_tile(st: Stream, V, A, stage, valu):
     slots = {}
     for i, text in enumerate(valu):
         slots.setdefault((START + 1 + (i * nm) // len(valu)) % nm, []).append(text)
-    dma_slots = {2: (0, 0), 5: (0, 1), 8: (1, 0), 11: (1, 1)}  # (tensor, piece)
-    nxt = (stage + 2) % 4
-    d0 = V["dma"]
+    ops, adv = dma_ops(V, (stage + 2) % 4)
     for g in range(nm):
-        if g in dma_slots:
-            x, i = dma_slots[g]
-            st.raw(f"s_add_u32 m0, {S_M0}, {nxt * STAGE + x * VOFF + i * 1024}")
-            st.raw("s_nop 0")
-            st.emit(f"buffer_load_dwordx4 v{d0 + i}, {RK if x == 0 else RV}, 0 offen lds")
-            if (x, i) == (1, 1):
-                for k in range(2):
-                    st.emit(f"v_add_u32 v{d0 + k}, s46, v{d0 + k}")
+        dma_at_gap(st, g, (2, 5, 8, 11), ops, adv)
         for text, rid in reads.get(g, []):
             st.emit(text, lds_id=rid)
         for text in slots.get(g, []):
@@ -426,98 +374,21 @@ def epilogue_dq(st: Stream, V, A):
                         f"offset:{64 * i + 16 * g}")
 
 
-def emit_probe(st: Stream, regs, karg_off, tmp=("v14", "v15")):
-    """Diagnostic builds only (tools/asm_probe.py): store `regs` of every lane of workgroup 0
-    to the debug buffer whose address follows the kernel's arguments, then end the wave."""
-    t0, t1 = tmp
-    st.raw(f"s_load_dwordx2 s[90:91], {S_KARG}, {karg_off}")
-    st.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-    st.raw("s_nop 15")
-    st.raw(f"v_mul_u32_u24 {t1}, {4 * len(regs)}, v0")
-    for k, r in enumerate(regs):
-        src = r
-        if r.startswith("a"):
-            st.raw(f"v_accvgpr_read_b32 {t0}, {r}")
-            st.raw("s_nop 1")
-            src = t0
-        elif r.startswith("s"):
-            st.raw(f"v_mov_b32 {t0}, {r}")
-            src = t0
-        st.raw(f"global_store_dword {t1}, {src}, s[90:91] offset:{4 * k}")
-        st.raw("s_waitcnt vmcnt(0)")
-    st.raw("s_endpgm")
-
-
-def gen_dq(probe=None):
-    """probe: (point, [registers]) -- a diagnostic build that dumps the registers at point
-    'prologue', 'tile0' (after the first tile) or 'loop' (after the loop)."""
+def gen_dq():
     V, A = regs_dq()
     st = Stream()
     prologue_dq(st, V, A)
-    if probe and probe[0] == "prologue":
-        emit_probe(st, probe[1], KARG_BYTES)
     valu = valu_stream(V)
     st.label(".Ldq_loop")
     for stage in range(4):
         emit_tile(st, V, A, stage, valu)
-        if probe and probe[0] == "tile0" and stage == 0:
-            emit_probe(st, probe[1], KARG_BYTES)
-    st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Ldq_loop")
+    loop_tail(st, S_ITER, ".Ldq_loop")
     emit_tail(st, V, A, valu)
-    if probe and probe[0] == "loop":
-        emit_probe(st, probe[1], KARG_BYTES)
     epilogue_dq(st, V, A)
     k = kernel_text("vd_attn_bwd_dq_d64", st.text(), vgprs=V.next, agprs=A.next, sgprs=96,
-                    lds_bytes=4 * STAGE, kernarg_bytes=KARG_BYTES + (8 if probe else 0),
+                    lds_bytes=4 * STAGE, kernarg_bytes=KARG_BYTES,
                     wg_size=64 * NW)
-    data = "\n.rodata\n.p2align 8\nvd_attn_dq_lanes:\n"
-    for row in lane_table():
-        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
-    return k, data, st
-
-
-def main():
-    out = sys.argv[1]
-    for arg in sys.argv[2:]:  # A/B builds only (tools/build_asm_phase.sh, build_asm_knobs.sh)
-        if arg.startswith("--phase="):
-            import asmgen
-            asmgen.PHASE_FLIP = arg[len("--phase="):]
-        elif arg.startswith("--knob="):  # --knob=module.NAME=int, e.g. gen_fwd.CHAINS=4
-            import importlib
-            target, val = arg[len("--knob="):].split("=")
-            mod, name = target.split(".")
-            m = sys.modules[__name__] if mod == "gen_attn_asm" else importlib.import_module(mod)
-            assert hasattr(m, name), target
-            setattr(m, name, int(val))
-    from gen_d128 import gen_dkdv128, gen_dq128
-    from gen_fwd128 import gen_fwd128
-    from gen_fwd import gen_fwd
-    from gen_d256 import gen_dq256
-    from gen_d256dk import gen_dkdv256
-    from gen_fwd256 import gen_fwd256
-    kdq, ddq, sdq = gen_dq()
-    kdk, ddk, sdk = gen_dkdv()
-    kfw, sfw = gen_fwd()
-    kdk2, ddk2, sdk2 = gen_dkdv128()
-    kdq2, sdq2 = gen_dq128()
-    kfw2, dfw2, sfw2 = gen_fwd128()
-    kdq4, ddq4, sdq4 = gen_dq256()
-    kdk4, ddk4, sdk4 = gen_dkdv256()
-    kfw4, sfw4 = gen_fwd256()
-    with open(out, "w") as f:
-        f.write("// generated by gen_attn_asm.py -- do not edit\n")
-        f.write(code_object_text([kdq, kdk, kfw, kdk2, kdq2, kfw2, kdq4, kdk4, kfw4],
-                                 ddq + ddk + ddk2 + dfw2 + ddq4 + ddk4))
-    if "--report" in sys.argv:
-        for name, st in (("dq", sdq), ("dkdv", sdk), ("fwd", sfw), ("dkdv128", sdk2),
-                         ("dq128", sdq2), ("fwd128", sfw2), ("dq256", sdq4),
-                         ("dkdv256", sdk4), ("fwd256", sfw4)):
-            print(f"{name}: {len(st.lines)} lines, {st.nops} nop wait states, {st.waits} lgkm "
-                  f"waits, {st.forced} forced by the 15-read limit ({st.young} on young reads)")
-
-
+    return k, lane_table_data("vd_attn_dq_lanes", lane_table()), st
 
 
 # ================================================================== dK / dV
@@ -582,52 +453,28 @@ def prologue_dkdv(st: Stream, V, A):
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
     r(f"s_load_dwordx4 s[48:51], {S_KARG}, 0x80")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S2_WAVE}, {V.r('tid')}")  # first lane's id = 64 * wave
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S2_WAVE}, {S2_WAVE}, 6")
-    r("s_getpc_b64 s[96:97]")
-    r("s_add_u32 s96, s96, vd_attn_dkdv_lanes@rel32@lo+4")
-    r("s_addc_u32 s97, s97, vd_attn_dkdv_lanes@rel32@hi+12")
+    wave_and_table(st, V, S2_WAVE, "s[96:97]", "vd_attn_dkdv_lanes")
     r("s_waitcnt lgkmcnt(0)")
     r(f"s_mul_i32 s52, {S_WGZ}, s35")
     r(f"s_add_u32 s52, s52, {S_WGY}")
-
-    def mad64(dlo, dhi, a, blo, bhi, t):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {t}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {t}")
-
-    mad64("s54", "s55", S_WGZ, "s36", "s37", "s58")
-    mad64("s58", "s59", S_WGY, "s38", "s39", "s99")
-    r("s_add_u32 s54, s54, s58")
-    r("s_addc_u32 s55, s55, s59")
-    mad64("s56", "s57", S_WGZ, "s40", "s41", "s58")
-    mad64("s58", "s59", S_WGY, "s42", "s43", "s99")
-    r("s_add_u32 s56, s56, s58")
-    r("s_addc_u32 s57, s57, s59")
-
-    def rsrc(dst, plo, phi, blo, bhi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {blo}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {bhi}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
-    rsrc(RQ2, "s16", "s17", "s54", "s55", "s46")
-    rsrc(RK2, "s18", "s19", "s54", "s55", "s46")
-    rsrc(RV2, "s20", "s21", "s54", "s55", "s46")
-    rsrc(RO2, "s22", "s23", "s56", "s57", "s47")
-    rsrc(RDK2, "s28", "s29", "s54", "s55", "s46")
-    rsrc(RDV2, "s30", "s31", "s54", "s55", "s46")
+    mad64(st, "s54", "s55", S_WGZ, "s36", "s37", "s58")
+    mad64(st, "s58", "s59", S_WGY, "s38", "s39", "s99")
+    add64(st, "s54", "s55", "s58", "s59")
+    mad64(st, "s56", "s57", S_WGZ, "s40", "s41", "s58")
+    mad64(st, "s58", "s59", S_WGY, "s42", "s43", "s99")
+    add64(st, "s56", "s57", "s58", "s59")
+    rsrc(st, RQ2, "s16", "s17", "s46", ("s54", "s55"))
+    rsrc(st, RK2, "s18", "s19", "s46", ("s54", "s55"))
+    rsrc(st, RV2, "s20", "s21", "s46", ("s54", "s55"))
+    rsrc(st, RO2, "s22", "s23", "s47", ("s56", "s57"))
+    rsrc(st, RDK2, "s28", "s29", "s46", ("s54", "s55"))
+    rsrc(st, RDV2, "s30", "s31", "s46", ("s54", "s55"))
     r("s_mul_i32 s58, s52, s32")
     r("s_mul_hi_u32 s59, s52, s32")
     r("s_lshl_b64 s[58:59], s[58:59], 2")
     r("s_lshl_b32 s99, s32, 2")
-    rsrc(RL2, "s24", "s25", "s58", "s59", "s99")
-    rsrc(RD2, "s26", "s27", "s58", "s59", "s99")
+    rsrc(st, RL2, "s24", "s25", "s99", ("s58", "s59"))
+    rsrc(st, RD2, "s26", "s27", "s99", ("s58", "s59"))
     # wave 1 stages delta, the others lse' (waves 2, 3 into the junk slot)
     r(f"s_cmp_eq_u32 {S2_WAVE}, 1")
     r("s_cselect_b64 s[56:57], s[80:81], s[76:77]")
@@ -670,14 +517,7 @@ def prologue_dkdv(st: Stream, V, A):
         e(f"v_mul_lo_u32 {V.r('stk', kj)}, {krow[kj]}, s33")
         e(f"v_add_u32 {V.r('stk', kj)}, {V.r('stk', kj)}, {V.r('dp', 54)}")
     r("s_waitcnt vmcnt(0)")
-    for w in range(32):
-        x = f"v{kv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s45, {t0}")
-        e(f"v_mul_f32 {t1}, s45, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('kf', w)}, {x}")
+    scale_bf16(st, kv, 32, "s45", t0, t1, lambda w: A.r("kf", w))
     # DMA source offsets: Q / dO pieces row * stride + chunk * 16 ; row constants 4 lane
     for i in range(2):
         e(f"v_mul_lo_u32 {V.r('dmao', i)}, {V.r('dmaq', i)}, s34")
@@ -709,7 +549,7 @@ def prologue_dkdv(st: Stream, V, A):
     for k in range(4):  # the loop's +32 KiB copies of the K^T / Q^T fragment offsets
         e(f"v_add_u32 {V.r('tmp', k)}, 0x8000, {V.r('troff', k)}")
     for t in range(3):
-        dk_dma(st, V, t, slots=None)
+        dma_issue(st, *dk_dma(V, t))
     r("s_waitcnt vmcnt(10)")
     r("s_barrier")
     st.flush_lds()
@@ -717,9 +557,9 @@ def prologue_dkdv(st: Stream, V, A):
         st.emit(text, lds_id=rid)
 
 
-def dk_dma(st: Stream, V, stage, slots):
+def dk_dma(V, stage):
     """The wave's 5 DMA ops of one tile into `stage` (Q pieces, dO pieces, its row-constant
-    piece), then advance the source offsets.  slots=None: emit now."""
+    piece) and the source-offset advances."""
     ops = []
     for x, (rs, nm) in enumerate(((RQ2, "dmaq"), (RO2, "dmao"))):
         for i in range(2):
@@ -732,14 +572,6 @@ def dk_dma(st: Stream, V, stage, slots):
            f"v_add_u32 {V.r('dmao', 0)}, s49, {V.r('dmao', 0)}",
            f"v_add_u32 {V.r('dmao', 1)}, s49, {V.r('dmao', 1)}",
            f"v_add_u32 {V.r('rcv')}, 0x100, {V.r('rcv')}"]
-    if slots is None:
-        for m0, ld in ops:
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-        for a in adv:
-            st.emit(a)
-        return None
     return ops, adv
 
 
@@ -848,30 +680,19 @@ def emit_dk_iter(st: Stream, V, A, stage, valu):
     put(2, dk_tr_reads(V, A, prev, 1))          # G(t-1, qb1) operands, tile t-1
     put(18, dk_row_reads(V, A, stage, 1))       # (t, qb1) fragments
     put(34, dk_tr_reads(V, A, stage, 0))        # G(t, qb0) operands
-    ops, adv = dk_dma(st, V, (stage + 3) % 4, slots=True)
-    dma_at = [49, 51, 53, 55, 57]
+    ops, adv = dk_dma(V, (stage + 3) % 4)
     for g in range(nm):
         if g == 48:
             st.raw("s_waitcnt vmcnt(5) lgkmcnt(0)")
             st.raw("s_barrier")
             st.flush_lds()
-            for text, rid in dk_row_reads(V, A, nxt, 0):
-                slots.setdefault(49 + 0, [])
             for k, (text, rid) in enumerate(dk_row_reads(V, A, nxt, 0)):
                 slots.setdefault(48 + k // 2, []).insert(k % 2, (text, rid))
-        if g in dma_at:
-            m0, ld = ops[dma_at.index(g)]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if g == dma_at[-1]:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, (49, 51, 53, 55, 57), ops, adv)
         for text, rid in slots.get(g, []):
             st.emit(text, lds_id=rid)
         text, deps = mf[g]
         st.emit(text, wait_lds=deps)
-    del prev
 
 
 def emit_dk_tail(st: Stream, V, A, valu):
@@ -917,18 +738,35 @@ def gen_dkdv():
     st.label(".Ldk_loop")
     for stage in range(4):
         emit_dk_iter(st, V, A, stage, valu)
-    st.raw(f"s_sub_u32 {S2_ITER}, {S2_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S2_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Ldk_loop")
+    loop_tail(st, S2_ITER, ".Ldk_loop")
     emit_dk_tail(st, V, A, valu)
     epilogue_dkdv(st, V, A)
     k = kernel_text("vd_attn_bwd_dkdv_d64", st.text(), vgprs=V.next, agprs=A.next, sgprs=100,
                     lds_bytes=DK_RC_BYTES + 4 * DK_STAGE, kernarg_bytes=DK_KARG,
                     wg_size=64 * NW)
-    data = "\n.rodata\n.p2align 8\nvd_attn_dkdv_lanes:\n"
-    for row in dk_lane_table():
-        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
-    return k, data, st
+    return k, lane_table_data("vd_attn_dkdv_lanes", dk_lane_table()), st
+
+
+# ================================================================== the driver
+# (report name, generator) in code-object order; a generator returns (kernel, [lane-table
+# .rodata,] stream).  The order fixes the layout of the code object.
+KERNELS = (("dq", gen_dq), ("dkdv", gen_dkdv), ("fwd", gen_fwd), ("dkdv128", gen_dkdv128),
+           ("dq128", gen_dq128), ("fwd128", gen_fwd128), ("dq256", gen_dq256),
+           ("dkdv256", gen_dkdv256), ("fwd256", gen_fwd256))
+
+
+def main():
+    out = sys.argv[1]
+    built = [(name, gen()) for name, gen in KERNELS]
+    with open(out, "w") as f:
+        f.write("// generated by gen_attn_asm.py -- do not edit\n")
+        f.write(code_object_text([b[0] for _, b in built],
+                                 "".join(d for _, b in built for d in b[1:-1])))
+    if "--report" in sys.argv:
+        for name, b in built:
+            st = b[-1]
+            print(f"{name}: {len(st.lines)} lines, {st.nops} nop wait states, {st.waits} lgkm "
+                  f"waits, {st.forced} forced by the 15-read limit ({st.young} on young reads)")
 
 
 if __name__ == "__main__":

@@ -22,7 +22,8 @@ the per-lane offsets.  The 128-element rows use attention.hip's swz_row<128> chu
 """
 from __future__ import annotations
 
-from asmgen import Regs, Stream, kernel_text
+from asmgen import (HI, Regs, Stream, add64, dma_at_gap, dma_issue, frag_offsets, kernel_text,
+                    lane_table_data, lds, loop_tail, mad64, rsrc, scale_bf16, swz, wave_and_table)
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4
@@ -35,8 +36,8 @@ RC_BYTES = 4 * RC
 NST = 4
 KARG = 144              # AsmDkdvArgs (vd_asm.h)
 START = 17
-HI = 65536
-# read / DMA placement knobs (A/B, tools/asm_ab_bwd128.py): first gap of each read group
+# read / DMA placement (variants measured in profiles/r03_ab_bwd128_knobs.txt): first gap of
+# each read group
 DK_TR0, DK_ROW1, DK_TR1 = 1, 18, 32
 DK_DMA0 = 49
 
@@ -49,16 +50,6 @@ S_WAVE, S_K0, S_M0, S_ITER, S_RCM0 = "s92", "s93", "s94", "s95", "s98"
 RRC = "s[56:59]"
 
 
-def swz(r):
-    """attention.hip swz_row<128>."""
-    return ((r & 3) << 2) | ((r >> 2) & 3)
-
-
-def toff_bytes(r, c):
-    """attention.hip toff<bf16, 128>(r, c) in bytes."""
-    return 2 * (r * D + (((c >> 3) ^ swz(r)) << 3) + (c & 7))
-
-
 def lane_table():
     """tab[wave][lane][32] u32: 0-7 row-fragment offsets (k-step s, block row 0), 8-15 the
     transposed-fragment offsets (2 i + hi: output-dim block i, rows +8 hi), 16-19 the DMA
@@ -67,22 +58,13 @@ def lane_table():
     out = []
     for w in range(NW):
         for lane in range(64):
-            r, hh = lane & 31, lane >> 5
-            row = [toff_bytes(r, 16 * s + 8 * hh) for s in range(8)]
-            g, fr = lane >> 4, lane & 15
-            q4, p4 = fr >> 2, fr & 3
-            tr = []
-            for i in range(4):
-                col = 32 * i + 16 * (g & 1) + 4 * p4
-                kr = 4 * (g >> 1) + q4
-                tr += [toff_bytes(kr, col), toff_bytes(kr + 8, col)]
             drow, dch = [], []
             for i in range(4):
                 gi = w * 4 + i
                 rr = gi * 4 + lane // 16
                 drow.append(rr)
-                dch.append(((lane % 16) ^ swz(rr)) * 16)
-            out.append(row + tr + drow + dch + [16 * hh] + [0] * 7)
+                dch.append(((lane % 16) ^ swz(D, rr)) * 16)
+            out.append(frag_offsets(D, lane, 8, 4) + drow + dch + [16 * (lane >> 5)] + [0] * 7)
     return out
 
 
@@ -108,13 +90,6 @@ def regs():
     A.alloc("orow", 32)      # dO row fragments [s]
     assert V.next <= 256 and A.next <= 256, (V.next, A.next)
     return V, A
-
-
-def lds(V, name, k, off):
-    """(base register, immediate) of LDS byte offset `off` from per-lane table entry k."""
-    if off >= HI:
-        return V.r({"rowoff": "rowhi", "troff": "trhi"}[name], k), off - HI
-    return V.r(name, k), off
 
 
 def row_reads(V, A, stage, qb):
@@ -213,52 +188,28 @@ def prologue(st: Stream, V, A):
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
     r(f"s_load_dwordx4 s[48:51], {S_KARG}, 0x80")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")  # first lane's id = 64 * wave
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
-    r("s_getpc_b64 s[96:97]")
-    r("s_add_u32 s96, s96, vd_attn_dkdv128_lanes@rel32@lo+4")
-    r("s_addc_u32 s97, s97, vd_attn_dkdv128_lanes@rel32@hi+12")
+    wave_and_table(st, V, S_WAVE, "s[96:97]", "vd_attn_dkdv128_lanes")
     r("s_waitcnt lgkmcnt(0)")
     r(f"s_mul_i32 s52, {S_WGZ}, s35")
     r(f"s_add_u32 s52, s52, {S_WGY}")
-
-    def mad64(dlo, dhi, a, blo, bhi, t):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {t}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {t}")
-
-    mad64("s54", "s55", S_WGZ, "s36", "s37", "s58")
-    mad64("s58", "s59", S_WGY, "s38", "s39", "s99")
-    r("s_add_u32 s54, s54, s58")
-    r("s_addc_u32 s55, s55, s59")
-    mad64("s56", "s57", S_WGZ, "s40", "s41", "s58")
-    mad64("s58", "s59", S_WGY, "s42", "s43", "s99")
-    r("s_add_u32 s56, s56, s58")
-    r("s_addc_u32 s57, s57, s59")
-
-    def rsrc(dst, plo, phi, blo, bhi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {blo}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {bhi}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
-    rsrc(RQ, "s16", "s17", "s54", "s55", "s46")
-    rsrc(RK, "s18", "s19", "s54", "s55", "s46")
-    rsrc(RV, "s20", "s21", "s54", "s55", "s46")
-    rsrc(RO, "s22", "s23", "s56", "s57", "s47")
-    rsrc(RDK, "s28", "s29", "s54", "s55", "s46")
-    rsrc(RDV, "s30", "s31", "s54", "s55", "s46")
+    mad64(st, "s54", "s55", S_WGZ, "s36", "s37", "s58")
+    mad64(st, "s58", "s59", S_WGY, "s38", "s39", "s99")
+    add64(st, "s54", "s55", "s58", "s59")
+    mad64(st, "s56", "s57", S_WGZ, "s40", "s41", "s58")
+    mad64(st, "s58", "s59", S_WGY, "s42", "s43", "s99")
+    add64(st, "s56", "s57", "s58", "s59")
+    rsrc(st, RQ, "s16", "s17", "s46", ("s54", "s55"))
+    rsrc(st, RK, "s18", "s19", "s46", ("s54", "s55"))
+    rsrc(st, RV, "s20", "s21", "s46", ("s54", "s55"))
+    rsrc(st, RO, "s22", "s23", "s47", ("s56", "s57"))
+    rsrc(st, RDK, "s28", "s29", "s46", ("s54", "s55"))
+    rsrc(st, RDV, "s30", "s31", "s46", ("s54", "s55"))
     r("s_mul_i32 s58, s52, s32")
     r("s_mul_hi_u32 s59, s52, s32")
     r("s_lshl_b64 s[58:59], s[58:59], 2")
     r("s_lshl_b32 s99, s32, 2")
-    rsrc(RL, "s24", "s25", "s58", "s59", "s99")
-    rsrc(RD, "s26", "s27", "s58", "s59", "s99")
+    rsrc(st, RL, "s24", "s25", "s99", ("s58", "s59"))
+    rsrc(st, RD, "s26", "s27", "s99", ("s58", "s59"))
     # wave 1 stages delta, the others lse' (waves 2, 3 into the junk slot)
     r(f"s_cmp_eq_u32 {S_WAVE}, 1")
     r("s_cselect_b64 s[56:57], s[80:81], s[76:77]")
@@ -298,14 +249,7 @@ def prologue(st: Stream, V, A):
     e(f"v_mul_lo_u32 {V.r('stk')}, {krow}, s33")
     e(f"v_add_u32 {V.r('stk')}, {V.r('stk')}, {h8}")
     r("s_waitcnt vmcnt(0)")
-    for w in range(32):
-        x = f"v{kv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s45, {t0}")
-        e(f"v_mul_f32 {t1}, s45, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('kf', w)}, {x}")
+    scale_bf16(st, kv, 32, "s45", t0, t1, lambda w: A.r("kf", w))
     # DMA source offsets: row * stride + chunk * 16 (the chunks were loaded into dmao)
     for i in range(4):
         e(f"v_mov_b32 {V.r('tmp', i)}, {V.r('dmao', i)}")
@@ -335,13 +279,7 @@ def prologue(st: Stream, V, A):
         e(f"ds_write_b128 {V.r('tmp2', 0)}, {V.r('tmp', 0, 4)} offset:{16 * k}")
     r("s_waitcnt lgkmcnt(0)")
     for t in range(3):
-        ops, adv = dma_ops(V, t)
-        for m0, ld in ops:
-            r(m0)
-            r("s_nop 0")
-            e(ld)
-        for a in adv:
-            e(a)
+        dma_issue(st, *dma_ops(V, t))
     r("s_waitcnt vmcnt(18)")
     r("s_barrier")
     st.flush_lds()
@@ -368,7 +306,7 @@ def emit_iter(st: Stream, V, A, stage, vlist):
     put(DK_ROW1, row_reads(V, A, stage, 1))  # (t, qb1) fragments: 18..29
     put(DK_TR1, tr_reads(V, A, stage, 0))    # G(t, qb0) operands: 32..47
     ops, adv = dma_ops(V, prev)
-    dma_at = list(range(DK_DMA0, DK_DMA0 + 9))
+    dma_at = tuple(range(DK_DMA0, DK_DMA0 + 9))
     for g in range(nm):
         if g == 48:
             st.raw("s_waitcnt vmcnt(9) lgkmcnt(0)")
@@ -376,14 +314,7 @@ def emit_iter(st: Stream, V, A, stage, vlist):
             st.flush_lds()
             for k, (text, rid) in enumerate(row_reads(V, A, nxt, 0)):
                 slots.setdefault(48 + k // 2, []).insert(k % 2, (text, rid))
-        if g in dma_at:
-            m0, ld = ops[dma_at.index(g)]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if g == dma_at[-1]:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, dma_at, ops, adv)
         for text, rid in slots.get(g, []):
             st.emit(text, lds_id=rid)
         text, deps = mf[g]
@@ -430,17 +361,12 @@ def gen_dkdv128():
     st.label(".Ldk128_loop")
     for stage in range(NST):
         emit_iter(st, V, A, stage, vlist)
-    st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Ldk128_loop")
+    loop_tail(st, S_ITER, ".Ldk128_loop")
     emit_tail(st, V, A, vlist)
     epilogue(st, V, A)
     k = kernel_text("vd_attn_bwd_dkdv_d128", st.text(), vgprs=V.next, agprs=A.next, sgprs=100,
                     lds_bytes=RC_BYTES + NST * STAGE, kernarg_bytes=KARG, wg_size=64 * NW)
-    data = "\n.rodata\n.p2align 8\nvd_attn_dkdv128_lanes:\n"
-    for row in lane_table():
-        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
-    return k, data, st
+    return k, lane_table_data("vd_attn_dkdv128_lanes", lane_table()), st
 
 
 # ================================================================== dQ
@@ -558,51 +484,27 @@ def dq_prologue(st: Stream, V, A):
     e, r = st.emit, st.raw
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S3_WAVE}, {V.r('tid')}")
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S3_WAVE}, {S3_WAVE}, 6")
-    r("s_getpc_b64 s[88:89]")
-    r("s_add_u32 s88, s88, vd_attn_dkdv128_lanes@rel32@lo+4")  # the dK/dV kernel's table
-    r("s_addc_u32 s89, s89, vd_attn_dkdv128_lanes@rel32@hi+12")
+    wave_and_table(st, V, S3_WAVE, "s[88:89]", "vd_attn_dkdv128_lanes")  # the dK/dV kernel's table
     r("s_waitcnt lgkmcnt(0)")
     r(f"s_mul_i32 s48, {S_WGZ}, s33")
     r(f"s_add_u32 s48, s48, {S_WGY}")
-
-    def mad64(dlo, dhi, a, blo, bhi, t):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {t}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {t}")
-
-    mad64("s50", "s51", S_WGZ, "s34", "s35", "s90")
-    mad64("s92", "s93", S_WGY, "s36", "s37", "s90")
-    r("s_add_u32 s50, s50, s92")
-    r("s_addc_u32 s51, s51, s93")
-    mad64("s52", "s53", S_WGZ, "s38", "s39", "s90")
-    mad64("s92", "s93", S_WGY, "s40", "s41", "s90")
-    r("s_add_u32 s52, s52, s92")
-    r("s_addc_u32 s53, s53, s93")
-
-    def rsrc(dst, plo, phi, blo, bhi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {blo}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {bhi}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
-    rsrc(RQ3, "s16", "s17", "s50", "s51", "s44")
-    rsrc(RK3, "s18", "s19", "s50", "s51", "s44")
-    rsrc(RV3, "s20", "s21", "s50", "s51", "s44")
-    rsrc(RO3, "s22", "s23", "s52", "s53", "s45")
-    rsrc(RDQ3, "s28", "s29", "s50", "s51", "s44")
+    mad64(st, "s50", "s51", S_WGZ, "s34", "s35", "s90")
+    mad64(st, "s92", "s93", S_WGY, "s36", "s37", "s90")
+    add64(st, "s50", "s51", "s92", "s93")
+    mad64(st, "s52", "s53", S_WGZ, "s38", "s39", "s90")
+    mad64(st, "s92", "s93", S_WGY, "s40", "s41", "s90")
+    add64(st, "s52", "s53", "s92", "s93")
+    rsrc(st, RQ3, "s16", "s17", "s44", ("s50", "s51"))
+    rsrc(st, RK3, "s18", "s19", "s44", ("s50", "s51"))
+    rsrc(st, RV3, "s20", "s21", "s44", ("s50", "s51"))
+    rsrc(st, RO3, "s22", "s23", "s45", ("s52", "s53"))
+    rsrc(st, RDQ3, "s28", "s29", "s44", ("s50", "s51"))
     r("s_mul_i32 s92, s48, s30")
     r("s_mul_hi_u32 s93, s48, s30")
     r("s_lshl_b64 s[92:93], s[92:93], 2")
     r("s_lshl_b32 s94, s30, 2")
-    rsrc(RL3, "s24", "s25", "s92", "s93", "s94")
-    rsrc(RD3, "s26", "s27", "s92", "s93", "s94")
+    rsrc(st, RL3, "s24", "s25", "s94", ("s92", "s93"))
+    rsrc(st, RD3, "s26", "s27", "s94", ("s92", "s93"))
     # q0 = wgx * 128 + wave * 32 ; M0 base of this wave's DMA pieces = wave * 4096
     r(f"s_lshl_b32 {S3_Q0}, {S_WGX}, 7")
     r(f"s_lshl_b32 s90, {S3_WAVE}, 5")
@@ -640,14 +542,7 @@ def dq_prologue(st: Stream, V, A):
     e(f"v_mul_lo_u32 {V.r('stq')}, {qrow}, s31")
     e(f"v_add_u32 {V.r('stq')}, {V.r('stq')}, {h8}")
     r("s_waitcnt vmcnt(0)")
-    for w in range(32):
-        x = f"v{qv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s43, {t0}")
-        e(f"v_mul_f32 {t1}, s43, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('qf', w)}, {x}")
+    scale_bf16(st, qv, 32, "s43", t0, t1, lambda w: A.r("qf", w))
     for k in range(16):
         e(f"v_mov_b32 {V.r('il', k)}, {V.r('tmp2', 0)}")
         e(f"v_mov_b32 {V.r('id', k)}, {V.r('tmp2', 1)}")
@@ -669,13 +564,7 @@ def dq_prologue(st: Stream, V, A):
         e(f"v_mov_b32 {V.r('sacc', k)}, 0")
         e(f"v_mov_b32 {V.r('dpacc', k)}, 0")
     for t in range(2):
-        ops, adv = dq_dma_ops(V, t)
-        for m0, ld in ops:
-            r(m0)
-            r("s_nop 0")
-            e(ld)
-        for a in adv:
-            e(a)
+        dma_issue(st, *dq_dma_ops(V, t))
 
 
 def dq_emit_tile(st: Stream, V, A, stage, vlist):
@@ -698,18 +587,11 @@ def dq_emit_tile(st: Stream, V, A, stage, vlist):
     put(DQ_KV1, dq_kv_reads(V, A, stage, 1))  # kb1 rows: 16..23 (consumed 32..47)
     put(DQ_TR1, dq_tr_reads(V, stage, 1))     # K^T kb1: 32..39
     ops, adv = dq_dma_ops(V, (stage + 2) % NST)
-    dma_at = list(DQ_DMA)
+    dma_at = DQ_DMA
     # the G products read the K^T fragments of the previous tile (no LDS wait of their own)
     mf = [(t, ()) if k < 8 or 24 <= k < 32 else (t, d) for k, (t, d) in enumerate(mf)]
     for g in range(nm):
-        if g in dma_at:
-            m0, ld = ops[dma_at.index(g)]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if g == dma_at[-1]:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, dma_at, ops, adv)
         for text, rid in slots.get(g, []):
             st.emit(text, lds_id=rid)
         text, deps = mf[g]
@@ -756,9 +638,7 @@ def gen_dq128():
     st.label(".Ldq128_loop")
     for stage in range(NST):
         dq_emit_tile(st, V, A, stage, vlist)
-    st.raw(f"s_sub_u32 {S3_ITER}, {S3_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S3_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Ldq128_loop")
+    loop_tail(st, S3_ITER, ".Ldq128_loop")
     dq_emit_tail(st, V, A, vlist)
     dq_epilogue(st, V, A)
     k = kernel_text("vd_attn_bwd_dq_d128", st.text(), vgprs=V.next, agprs=A.next, sgprs=96,

@@ -28,7 +28,9 @@ grid alone is 128 workgroups, half the chip.
 """
 from __future__ import annotations
 
-from asmgen import Regs, Stream, kernel_text
+from asmgen import (HI, Regs, Stream, add64, dma_at_gap, dma_issue, frag_offsets, kernel_text,
+                    lane_table_data, loop_tail, mad64, rsrc, scale_bf16, swz, toff_bytes,
+                    wave_and_table)
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4
@@ -37,7 +39,6 @@ KT = 32                 # keys per tile
 KTILE = 16384           # one 32 x 256 bf16 tile; K tiles of the 4 stages in [0, 64 KiB),
 VBASE = 65536           # V tiles in [64 KiB, 128 KiB): every K / K^T read stays within the
 NST = 4                 # 16-bit ds_read immediate
-HI = 65536
 KARG = 160              # AsmDq256Args (vd_asm.h)
 RING = 8                # K / V row-fragment ring slots (4 VGPRs each)
 TRING = 8               # K^T fragment ring slots (4 VGPRs each: lo 2 + hi 2)
@@ -57,18 +58,9 @@ RQ, RK, RV, RO, RL, RD, RDQ, RP = ("s[56:59]", "s[60:63]", "s[64:67]", "s[68:71]
 S_WAVE, S_Q0, S_M0, S_ITER, S_SEQ, S_SPLIT, S_ZS, S_X = ("s88", "s89", "s90", "s91", "s92",
                                                           "s93", "s94", "s95")
 S_T0, S_T1, S_T2, S_T3 = "s96", "s97", "s98", "s99"   # two aligned pairs
+S_T01 = (S_T0, S_T1)    # the byte offset every buffer resource of the prologue is based at
 S_TAB = "s[100:101]"
 DMA_AT = tuple(range(17, 32, 2))   # the 8 LDS-DMA pieces: odd gaps of the G group
-
-
-def swz(r):
-    """attention.hip swz_row<256> (= <128>): 4-bit chunk XOR of row r."""
-    return ((r & 3) << 2) | ((r >> 2) & 3)
-
-
-def toff_bytes(r, c):
-    """attention.hip toff<bf16, 256>(r, c) in bytes."""
-    return 2 * (r * D + (((c >> 3) ^ swz(r)) << 3) + (c & 7))
 
 
 def lane_table():
@@ -79,28 +71,19 @@ def lane_table():
     out = []
     for w in range(NW):
         for lane in range(64):
-            r, hh = lane & 31, lane >> 5
-            row = [toff_bytes(r, 16 * s + 8 * hh) for s in range(8)]
-            g, fr = lane >> 4, lane & 15
-            q4, p4 = fr >> 2, fr & 3
-            tr = []
-            for i in range(4):
-                col = 32 * i + 16 * (g & 1) + 4 * p4
-                kr = 4 * (g >> 1) + q4
-                tr += [toff_bytes(kr, col), toff_bytes(kr + 8, col)]
             drow, dch = [], []
             for i in range(4):
                 gi = w * 4 + i
                 rr = gi * 2 + lane // 32
                 drow.append(rr)
-                dch.append(((lane % 32) ^ swz(rr)) * 16)
-            out.append(row + tr + drow + dch + [0] * 8)
+                dch.append(((lane % 32) ^ swz(D, rr)) * 16)
+            out.append(frag_offsets(D, lane, 8, 4) + drow + dch + [0] * 8)
     # checks of the +256 B / +8192 B immediates the kernel relies on
     for r in range(32):
         for c in range(0, 128, 8):
-            assert toff_bytes(r, c + 128) == toff_bytes(r, c) + 256
+            assert toff_bytes(D, r, c + 128) == toff_bytes(D, r, c) + 256
     for r in range(16):
-        assert toff_bytes(r + 16, 0) == toff_bytes(r, 0) + 8192
+        assert toff_bytes(D, r + 16, 0) == toff_bytes(D, r, 0) + 8192
     return out
 
 
@@ -198,13 +181,7 @@ def prologue(st: Stream, V, A):
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
     r(f"s_load_dwordx8 s[48:55], {S_KARG}, 0x80")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
-    r(f"s_getpc_b64 {S_TAB}")
-    r("s_add_u32 s100, s100, vd_attn_d256_lanes@rel32@lo+4")
-    r("s_addc_u32 s101, s101, vd_attn_d256_lanes@rel32@hi+12")
+    wave_and_table(st, V, S_WAVE, S_TAB, "vd_attn_d256_lanes")
     r("s_waitcnt lgkmcnt(0)")
     # grid.z = (sequence group z') << lsplit | split
     r(f"s_lshl_b32 {S_X}, 1, s51")
@@ -214,30 +191,12 @@ def prologue(st: Stream, V, A):
     r(f"s_mul_i32 {S_SEQ}, {S_ZS}, s33")
     r(f"s_add_u32 {S_SEQ}, {S_SEQ}, {S_WGY}")
 
-    def mad64(dlo, dhi, a, blo, bhi):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {S_X}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {S_X}")
-
-    def add64():  # T0:T1 += T2:T3
-        r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
-        r(f"s_addc_u32 {S_T1}, {S_T1}, {S_T3}")
-
-    def rsrc(dst, plo, phi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {S_T0}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {S_T1}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
     # q / dq sequence base
-    mad64(S_T0, S_T1, S_ZS, "s34", "s35")
-    mad64(S_T2, S_T3, S_WGY, "s36", "s37")
-    add64()
-    rsrc(RQ, "s16", "s17", "s44")
-    rsrc(RDQ, "s28", "s29", "s44")
+    mad64(st, S_T0, S_T1, S_ZS, "s34", "s35", S_X)
+    mad64(st, S_T2, S_T3, S_WGY, "s36", "s37", S_X)
+    add64(st, S_T0, S_T1, S_T2, S_T3)
+    rsrc(st, RQ, "s16", "s17", "s44", S_T01)
+    rsrc(st, RDQ, "s28", "s29", "s44", S_T01)
     # K / V: this split's keys [split * kps, min(n, (split + 1) * kps)): base += split * kps
     # * ts_bytes, range (keys - 1) * ts_bytes + 512 (the host keeps every split non-empty)
     r(f"s_mul_i32 {S_T2}, {S_SPLIT}, s50")       # first key of the split
@@ -250,27 +209,27 @@ def prologue(st: Stream, V, A):
     r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
     r(f"s_addc_u32 {S_T1}, {S_T1}, 0")
     r(f"s_mov_b32 {S_T3}, {S_X}")
-    rsrc(RK, "s18", "s19", S_T3)
-    rsrc(RV, "s20", "s21", S_T3)
+    rsrc(st, RK, "s18", "s19", S_T3, S_T01)
+    rsrc(st, RV, "s20", "s21", S_T3, S_T01)
     # dout base
-    mad64(S_T0, S_T1, S_ZS, "s38", "s39")
-    mad64(S_T2, S_T3, S_WGY, "s40", "s41")
-    add64()
-    rsrc(RO, "s22", "s23", "s45")
+    mad64(st, S_T0, S_T1, S_ZS, "s38", "s39", S_X)
+    mad64(st, S_T2, S_T3, S_WGY, "s40", "s41", S_X)
+    add64(st, S_T0, S_T1, S_T2, S_T3)
+    rsrc(st, RO, "s22", "s23", "s45", S_T01)
     # lse' / delta rows of the sequence: seq * n * 4, range n * 4
     r(f"s_mul_i32 {S_T0}, {S_SEQ}, s30")
     r(f"s_mul_hi_u32 {S_T1}, {S_SEQ}, s30")
     r(f"s_lshl_b64 s[96:97], s[96:97], 2")
     r(f"s_lshl_b32 {S_T2}, s30, 2")
-    rsrc(RL, "s24", "s25", S_T2)
-    rsrc(RD, "s26", "s27", S_T2)
+    rsrc(st, RL, "s24", "s25", S_T2, S_T01)
+    rsrc(st, RD, "s26", "s27", S_T2, S_T01)
     # fp32 partials: part + split * split_bytes + seq * n * 1024, range n * 1024
-    mad64(S_T0, S_T1, S_SPLIT, "s52", "s53")
+    mad64(st, S_T0, S_T1, S_SPLIT, "s52", "s53", S_X)
     r(f"s_mul_i32 {S_T2}, {S_SEQ}, s30")
     r(f"s_mul_hi_u32 {S_T3}, {S_SEQ}, s30")
     r(f"s_lshl_b64 s[98:99], s[98:99], 10")
-    add64()
-    rsrc(RP, "s48", "s49", "s54")
+    add64(st, S_T0, S_T1, S_T2, S_T3)
+    rsrc(st, RP, "s48", "s49", "s54", S_T01)
     # q0 = wgx * 128 + wave * 32 ; M0 base of this wave's DMA pieces = wave * 4096
     r(f"s_lshl_b32 {S_Q0}, {S_WGX}, 7")
     r(f"s_lshl_b32 {S_X}, {S_WAVE}, 5")
@@ -318,14 +277,7 @@ def prologue(st: Stream, V, A):
     e(f"v_add_u32 {V.r('stq')}, {V.r('stq')}, {h8}")
     st.label(".Ldq256_st_done")
     r("s_waitcnt vmcnt(0)")
-    for w in range(64):
-        x = f"v{qv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s43, {t0}")
-        e(f"v_mul_f32 {t1}, s43, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('qf', w)}, {x}")
+    scale_bf16(st, qv, 64, "s43", t0, t1, lambda w: A.r("qf", w))
     for k in range(16):
         e(f"v_mov_b32 {V.r('il', k)}, {V.r('tmp2', 0)}")
         e(f"v_mov_b32 {V.r('id', k)}, {V.r('tmp2', 1)}")
@@ -351,13 +303,7 @@ def prologue(st: Stream, V, A):
         e(f"v_mov_b32 {V.r('sacc', k)}, 0")
         e(f"v_mov_b32 {V.r('dpacc', k)}, 0")
     for t in range(2):
-        ops, adv = dma_ops(V, t)
-        for m0, ld in ops:
-            r(m0)
-            r("s_nop 0")
-            e(ld)
-        for a in adv:
-            e(a)
+        dma_issue(st, *dma_ops(V, t))
 
 
 def emit_body(st: Stream, V, A, stage):
@@ -404,14 +350,7 @@ def emit_body(st: Stream, V, A, stage):
             at(16 + j - TR_AHEAD, item)
     ops, adv = dma_ops(V, (stage + 2) % NST)
     for g in range(nm):
-        if g in DMA_AT:
-            m0, ld = ops[DMA_AT.index(g)]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if g == DMA_AT[-1]:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, DMA_AT, ops, adv)
         for text, rid in slots.get(g, []):
             st.emit(text, lds_id=rid)
         text, deps = mf[g]
@@ -472,14 +411,9 @@ def gen_dq256():
     st.label(".Ldq256_loop")
     for stage in range(NST):
         emit_body(st, V, A, stage)
-    st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Ldq256_loop")
+    loop_tail(st, S_ITER, ".Ldq256_loop")
     emit_tail(st, V, A)
     epilogue(st, V, A)
     k = kernel_text("vd_attn_bwd_dq_d256", st.text(), vgprs=V.next, agprs=A.next, sgprs=102,
                     lds_bytes=VBASE + NST * KTILE, kernarg_bytes=KARG, wg_size=64 * NW)
-    data = "\n.rodata\n.p2align 8\nvd_attn_d256_lanes:\n"
-    for row in lane_table():
-        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
-    return k, data, st
+    return k, lane_table_data("vd_attn_d256_lanes", lane_table()), st

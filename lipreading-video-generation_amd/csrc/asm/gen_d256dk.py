@@ -31,8 +31,9 @@ attn_dkdv_sum_kernel adds.
 """
 from __future__ import annotations
 
-from asmgen import Regs, Stream, kernel_text
-from gen_d256 import swz, toff_bytes
+from asmgen import (HI, Regs, Stream, add64, dma_at_gap, dma_issue, frag_offsets, kernel_text,
+                    lane_table_data, lds, loop_tail, mad64, rsrc, scale_bf16, swz, table_addr,
+                    wave_id)
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4
@@ -40,7 +41,6 @@ D = 256
 STAGE = 32768           # Q tile | dO tile (32 x 256 bf16 each)
 OOFF = 16384
 NST = 4
-HI = 65536
 RC_BASE = NST * STAGE   # 131072: per stage lse' (256 B) | delta (256 B) | junk (256 B)
 RC = 768
 PX_BASE = RC_BASE + NST * RC   # P exchange [parity][pair] x 4 KiB
@@ -67,6 +67,7 @@ R_DMA, R_RC, R_OUT, R_KV = "s[60:63]", "s[64:67]", "s[68:71]", "s[72:75]"
 S_WAVE, S_K0, S_M0, S_ITER, S_RCM0, S_SEQ, S_ZS, S_SPLIT, S_X, S_PAIR = (
     "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85")
 S_T0, S_T1, S_T2, S_T3 = "s86", "s87", "s88", "s89"   # two aligned pairs
+S_T01 = (S_T0, S_T1)    # the byte offset every buffer resource of the prologue is based at
 S_TAB = "s[90:91]"
 
 
@@ -79,22 +80,13 @@ def lane_table():
     for w in range(NW):
         pair = w & 1
         for lane in range(64):
-            r, hh = lane & 31, lane >> 5
-            row = [toff_bytes(r, 16 * s + 8 * hh) for s in range(8)]
-            g, fr = lane >> 4, lane & 15
-            q4, p4 = fr >> 2, fr & 3
-            tr = []
-            for i in range(4):
-                col = 32 * i + 16 * (g & 1) + 4 * p4
-                kr = 4 * (g >> 1) + q4
-                tr += [toff_bytes(kr, col), toff_bytes(kr + 8, col)]
             drow, dch = [], []
             for i in range(8):
                 gi = pair * 8 + i
                 rr = gi * 2 + lane // 32
                 drow.append(rr)
-                dch.append(((lane % 32) ^ swz(rr)) * 16)
-            out.append(row + tr + drow + dch)
+                dch.append(((lane % 32) ^ swz(D, rr)) * 16)
+            out.append(frag_offsets(D, lane, 8, 4) + drow + dch)
     return out
 
 
@@ -135,12 +127,6 @@ def regs_b():
     return V, A
 
 
-def lds(V, base, k, off):
-    if off >= HI:
-        return V.r({"rowoff": "rowhi", "troff": "trhi"}[base], k), off - HI
-    return V.r(base, k), off
-
-
 def row_read(V, A, stage, s, half):
     """Row fragment of k-step s of the Q (half 0) / dO (half 1) tile into ring slot s % 8."""
     off = stage * STAGE + half * OOFF + (256 if s >= 8 else 0)
@@ -168,7 +154,7 @@ def rc_reads(V, stage, which, dst):
              f"{stage * RC + 256 * which + 32 * g}", ("C", g)) for g in range(4)]
 
 
-def dma_ops(V, stage, half, _unused, rc_rs):
+def dma_ops(V, stage, half, rc_rs):
     """The wave's 9 DMA ops of one tile: its 8 row pieces of the Q (half 0) / dO (1) tile
     into `stage`, then its row-constant piece (rc_slot 0 lse', 1 delta, 2 junk)."""
     ops = []
@@ -190,14 +176,9 @@ def prologue_common(st: Stream, V):
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
     r(f"s_load_dwordx8 s[48:55], {S_KARG}, 0x80")
     r(f"s_load_dwordx4 s[56:59], {S_KARG}, 0xa0")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
+    wave_id(st, V, S_WAVE)
     r(f"s_and_b32 {S_PAIR}, {S_WAVE}, 1")
-    r(f"s_getpc_b64 {S_TAB}")
-    r("s_add_u32 s90, s90, vd_attn_d256dk_lanes@rel32@lo+4")
-    r("s_addc_u32 s91, s91, vd_attn_d256dk_lanes@rel32@hi+12")
+    table_addr(st, S_TAB, "vd_attn_d256dk_lanes")
     r("s_waitcnt lgkmcnt(0)")
     r(f"s_lshl_b32 {S_X}, 1, s55")
     r(f"s_sub_u32 {S_X}, {S_X}, 1")
@@ -237,26 +218,9 @@ def seq_bases(st: Stream, half):
     r = st.raw
     bsl, bsh, gsl, gsh, ts = (("s36", "s37", "s38", "s39", "s33") if half == 0 else
                               ("s40", "s41", "s42", "s43", "s34"))
-    r(f"s_mul_i32 {S_T0}, {S_ZS}, {bsl}")
-    r(f"s_mul_hi_u32 {S_T1}, {S_ZS}, {bsl}")
-    r(f"s_mul_i32 {S_X}, {S_ZS}, {bsh}")
-    r(f"s_add_u32 {S_T1}, {S_T1}, {S_X}")
-    r(f"s_mul_i32 {S_T2}, {S_WGY}, {gsl}")
-    r(f"s_mul_hi_u32 {S_T3}, {S_WGY}, {gsl}")
-    r(f"s_mul_i32 {S_X}, {S_WGY}, {gsh}")
-    r(f"s_add_u32 {S_T3}, {S_T3}, {S_X}")
-    r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
-    r(f"s_addc_u32 {S_T1}, {S_T1}, {S_T3}")
-
-
-def rsrc(st, dst, plo, phi, nrec):
-    r = st.raw
-    d0 = int(dst[2:].split(":")[0])
-    r(f"s_add_u32 s{d0}, {plo}, {S_T0}")
-    r(f"s_addc_u32 s{d0 + 1}, {phi}, {S_T1}")
-    r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-    r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-    r(f"s_mov_b32 s{d0 + 3}, 0x20000")
+    mad64(st, S_T0, S_T1, S_ZS, bsl, bsh, S_X)
+    mad64(st, S_T2, S_T3, S_WGY, gsl, gsh, S_X)
+    add64(st, S_T0, S_T1, S_T2, S_T3)
 
 
 def prologue_role(st: Stream, V, A, role):
@@ -267,23 +231,19 @@ def prologue_role(st: Stream, V, A, role):
     ts = "s33" if role == 0 else "s34"
     # this sequence's K / V rows (the keys are not split)
     seq_bases(st, 0)
-    rsrc(st, R_KV, "s18" if role == 0 else "s20", "s19" if role == 0 else "s21", "s46")
+    rsrc(st, R_KV, "s18" if role == 0 else "s20", "s19" if role == 0 else "s21", "s46", S_T01)
     # output rows: bf16 dK / dV of the sequence, or the fp32 partials of the split
     r("s_cmp_eq_u64 s[52:53], 0")
     r(f"s_cbranch_scc0 .Ldk256_{role}_part")
-    rsrc(st, R_OUT, "s30" if role == 0 else "s28", "s31" if role == 0 else "s29", "s46")
+    rsrc(st, R_OUT, "s30" if role == 0 else "s28", "s31" if role == 0 else "s29", "s46", S_T01)
     r(f"s_branch .Ldk256_{role}_out")
     st.label(f".Ldk256_{role}_part")
-    r(f"s_mul_i32 {S_T0}, {S_SPLIT}, s56")
-    r(f"s_mul_hi_u32 {S_T1}, {S_SPLIT}, s56")
-    r(f"s_mul_i32 {S_X}, {S_SPLIT}, s57")
-    r(f"s_add_u32 {S_T1}, {S_T1}, {S_X}")
+    mad64(st, S_T0, S_T1, S_SPLIT, "s56", "s57", S_X)
     r(f"s_mul_i32 {S_T2}, {S_SEQ}, s32")      # seq * nkv rows of 2 KiB
     r(f"s_mul_hi_u32 {S_T3}, {S_SEQ}, s32")
     r("s_lshl_b64 s[88:89], s[88:89], 11")
-    r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
-    r(f"s_addc_u32 {S_T1}, {S_T1}, {S_T3}")
-    rsrc(st, R_OUT, "s52", "s53", "s58")
+    add64(st, S_T0, S_T1, S_T2, S_T3)
+    rsrc(st, R_OUT, "s52", "s53", "s58", S_T01)
     st.label(f".Ldk256_{role}_out")
     # the split's Q / dO rows: base + split * qps * stride, range (queries - 1) * stride + 512
     seq_bases(st, half)
@@ -296,7 +256,7 @@ def prologue_role(st: Stream, V, A, role):
     r(f"s_sub_u32 {S_X}, {S_T3}, 1")
     r(f"s_mul_i32 {S_X}, {S_X}, {ts}")
     r(f"s_add_u32 {S_X}, {S_X}, 512")
-    rsrc(st, R_DMA, "s16" if role == 0 else "s22", "s17" if role == 0 else "s23", S_X)
+    rsrc(st, R_DMA, "s16" if role == 0 else "s22", "s17" if role == 0 else "s23", S_X, S_T01)
     # row constants of the split: (seq * n + split * qps) * 4, range queries * 4; pair 1
     # waves DMA theirs into the junk slot
     r(f"s_lshl_b32 {S_X}, {S_T3}, 2")
@@ -305,7 +265,7 @@ def prologue_role(st: Stream, V, A, role):
     r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
     r(f"s_mov_b32 {S_T1}, 0")
     r(f"s_lshl_b64 s[86:87], s[86:87], 2")
-    rsrc(st, R_RC, "s24" if role == 0 else "s26", "s25" if role == 0 else "s27", S_X)
+    rsrc(st, R_RC, "s24" if role == 0 else "s26", "s25" if role == 0 else "s27", S_X, S_T01)
     r(f"s_movk_i32 {S_RCM0}, 0x200")
     r(f"s_cmp_eq_u32 {S_PAIR}, 0")
     r(f"s_cselect_b32 {S_RCM0}, {256 * role}, {S_RCM0}")
@@ -343,15 +303,7 @@ def prologue_role(st: Stream, V, A, role):
     st.label(f".Ldk256_{role}_sdone")
     r("s_waitcnt vmcnt(0)")
     if role == 0:
-        t0, t1 = V.r("tmp", 0), V.r("tmp", 1)
-        for w in range(64):
-            x = f"v{stage0 + w}"
-            e(f"v_lshlrev_b32 {t0}, 16, {x}")
-            e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-            e(f"v_mul_f32 {t0}, s45, {t0}")
-            e(f"v_mul_f32 {t1}, s45, {t1}")
-            e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-            e(f"v_accvgpr_write_b32 {A.r('kf', w)}, {x}")
+        scale_bf16(st, stage0, 64, "s45", V.r("tmp", 0), V.r("tmp", 1), lambda w: A.r("kf", w))
     # DMA source offsets of tile 0 (rows * stride + chunk), the +64 KiB offset copies
     for i in range(8):
         e(f"v_mul_lo_u32 {V.r('dma', i)}, {V.r('dma', i)}, {ts}")
@@ -375,13 +327,7 @@ def prologue_role(st: Stream, V, A, role):
         for k in range(8):
             e(f"v_mov_b32 {V.r('dsb', k)}, 0")
     for t in range(2):
-        ops, adv = dma_ops(V, t, half, None, R_RC)
-        for m0, ld in ops:
-            r(m0)
-            r("s_nop 0")
-            e(ld)
-        for a in adv:
-            e(a)
+        dma_issue(st, *dma_ops(V, t, half, R_RC))
 
 
 def zero_lds(st: Stream, V):
@@ -447,7 +393,7 @@ def emit_body_a(st: Stream, V, A, stage):
                    f"offset:{par * 2 * PX + g * 1024}", None))
     for k, item in enumerate(vl):
         at(17 + (k * 14) // len(vl), item)
-    ops, adv = dma_ops(V, (stage + 2) % NST, 0, None, R_RC)
+    ops, adv = dma_ops(V, (stage + 2) % NST, 0, R_RC)
     emit_slots(st, mf, slots, ops, adv)
 
 
@@ -498,20 +444,13 @@ def emit_body_b(st: Stream, V, A, stage):
                (f"v_cvt_pk_bf16_f32 {V.r('dsb', k)}, v{dprev + a}, v{dprev + b}", None)]
     for k, item in enumerate(vl):
         at(2 + (k * 12) // len(vl), item)
-    ops, adv = dma_ops(V, (stage + 2) % NST, 1, None, R_RC)
+    ops, adv = dma_ops(V, (stage + 2) % NST, 1, R_RC)
     emit_slots(st, mf, slots, ops, adv)
 
 
 def emit_slots(st: Stream, mf, slots, ops, adv):
     for g in range(len(mf)):
-        if g in DMA_AT:
-            m0, ld = ops[DMA_AT.index(g)]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if g == DMA_AT[-1]:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, DMA_AT, ops, adv)
         for text, rid in slots.get(g, []):
             if rid is not None and rid[0] in ("R", "T", "C") or (rid is not None and rid[0] == "P"
                                                                    and text.startswith("ds_read")):
@@ -609,9 +548,7 @@ def gen_dkdv256():
         st.label(f".Ldk256_{role}_loop")
         for stage in range(NST):
             body(st, V, A, stage)
-        st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-        st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-        st.raw(f"s_cbranch_scc1 .Ldk256_{role}_loop")
+        loop_tail(st, S_ITER, f".Ldk256_{role}_loop")
         emit_tail(st, V, A, role)
         epilogue(st, V, A, role)
         if role == 0:
@@ -620,7 +557,4 @@ def gen_dkdv256():
     ag = max(AA.next, AB.next)
     k = kernel_text("vd_attn_bwd_dkdv_d256", st.text(), vgprs=vg, agprs=ag, sgprs=92,
                     lds_bytes=LDS_BYTES, kernarg_bytes=KARG, wg_size=64 * NW)
-    data = "\n.rodata\n.p2align 8\nvd_attn_d256dk_lanes:\n"
-    for row in lane_table():
-        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
-    return k, data, st
+    return k, lane_table_data("vd_attn_d256dk_lanes", lane_table()), st

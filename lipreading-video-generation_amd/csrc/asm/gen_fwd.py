@@ -27,7 +27,9 @@ iteration, which is its own copy of the 8 bodies.
 """
 from __future__ import annotations
 
-from asmgen import Regs, Stream, kernel_text
+from asmgen import (COST, HI, Regs, Stream, add64, combine_list, dma_at_gap, dma_issue,
+                    kernel_text, lds, loop_tail, mad64, place, rare_targets, rsrc, scale_bf16,
+                    wave_and_table)
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4
@@ -36,20 +38,18 @@ PD = 4                 # prefetch distance (tiles)
 STAGE = 16384          # K tile | V tile
 VOFF = 8192
 KARG = 112
-HI = 65536             # ds_read immediates are 16 bits: stages >= 4 use the +64 KiB bases
 NINF, PINF = "0xff800000", "0x7f800000"
-BAR2 = False           # A/B (tools/asm_ab.py): one barrier per two bodies
 CHECK_NOP = 3          # wait states between the check's v_cmp and its branch
-DROP = 0               # timing experiments only (wrong results): 1 exp, 2 add, 4 cvt, 8 reads,
-                       # 16 the loop's LDS-DMA pieces
 CHAINS = 1             # row-sum accumulators per query block (1: one dependent add chain;
                        # 14.24 vs 14.42 ms for 4, profiles/r03_ab_fwd_knobs.txt)
-NORARE = 0             # timing experiment only: never take the rare path (wrong results)
-STAMP = 0              # diagnostic: store loop cycles / realtime per workgroup (karg 112)
-GSGS = 0               # MFMA order of a body: 0 G(kb0) G(kb1) S(kb0) S(kb1); 1 G S G S
-LAG1 = 0               # CHAINS = 1 through the lagged list (adds 4 scores behind their exps)
-DMAS = 0               # LDS-DMA slots of a body: 0 {4,12,20,28} 1 {1,9,17,25} 2 {6,14,22,30}
-                       # 3 {0,8,16,24}
+DMA_AT = (4, 12, 20, 28)   # LDS-DMA gaps of a body
+# Measured and removed (head_dim-64 forward, N = 262144): one barrier per two bodies (BAR2)
+# 14.39 vs 14.42 ms and the MFMA order G S G S (GSGS) 14.60 vs 14.42 ms,
+# profiles/r03_ab_fwd_knobs.txt; the single add chain through the lagged list (LAG1) 13.91
+# vs 13.78 ms and the DMA gaps {1,9,17,25} / {6,14,22,30} / {0,8,16,24} (DMAS) 13.76 / 13.75
+# / 13.91 vs 13.78 ms, profiles/r03_ab_fwd_knobs2.txt.  The cost attribution builds that
+# dropped instructions or the rare path (wrong results) and the cycle stamps:
+# profiles/r03_fwd_cycle_attribution.txt.
 MSUM = 0               # row sums on the matrix pipe: 8 MFMAs (ones x P^T) per body replace the
                        # 64 v_add_f32; the tile's lagged-max check moves to the next body's top.
                        # 1: 32x32x16 (ones x P^T); 2: 16x16x32 with a lane-group selector as
@@ -95,17 +95,10 @@ def sblk(V, par, p):
     return V.r(f"s{par}", 16 * p, 16)
 
 
-def lds(V, base, off):
-    """(base register, immediate) of an LDS byte offset `off` from a per-lane table entry."""
-    if off >= HI:
-        return V.r({"rowoff": "rowhi", "troff": "trhi"}[base[0]], base[1]), off - HI
-    return V.r(base[0], base[1]), off
-
-
 def k_reads(V, A, stage, kb):
     out = []
     for s in range(4):
-        b, off = lds(V, ("rowoff", s), stage * STAGE + kb * 4096)
+        b, off = lds(V, "rowoff", s, stage * STAGE + kb * 4096)
         out.append((f"ds_read_b128 {A.r('kf', 16 * kb + 4 * s, 4)}, {b} offset:{off}",
                     ("K", kb, s)))
     return out
@@ -116,7 +109,7 @@ def tr_reads(V, A, stage, kb):
     for i in range(2):
         for s2 in range(2):
             for hi in range(2):
-                b, off = lds(V, ("troff", 2 * i + hi), stage * STAGE + VOFF + kb * 4096 + s2 * 2048)
+                b, off = lds(V, "troff", 2 * i + hi, stage * STAGE + VOFF + kb * 4096 + s2 * 2048)
                 out.append((f"ds_read_b64_tr_b16 {A.r('trf', 16 * kb + 8 * i + 4 * s2 + 2 * hi, 2)}"
                             f", {b} offset:{off}", ("T", kb, i, s2, hi)))
     return out
@@ -177,9 +170,6 @@ def s_mfmas(V, A, par, kb, zero_c=False):
 
 
 # ------------------------------------------------------------------ softmax stream
-COST = {"exp": 8.0, "add": 4.0, "cvt": 4.5, "cmp": 4.0, "cnd": 4.0}
-
-
 def softmax_list(V, par, masked, u):
     """The VALU of one tile's softmax: [(text, cost, earliest gap)] in issue order.  Per
     score: v_exp_f32, an add into one of CHAINS row-sum accumulators of its query block
@@ -187,8 +177,7 @@ def softmax_list(V, par, masked, u):
     previous add is waited for), half a v_cvt_pk_bf16_f32.  A slot's bf16 P^T is written
     only after G(t-1) of the same key block has read the previous tile's (earliest gap).
     Masked tiles set keys >= n to -inf first (klim = keys left - 4 hh)."""
-    kinds = {"v_exp_f32": 1, "v_add_f32": 2, "v_mov_b32": 2, "v_cvt_pk_bf16_f32": 4}
-    gk = {0: 9, 1: 25} if GSGS else {0: 9, 1: 17}
+    gk = {0: 9, 1: 17}
     out = []
     if MSUM:
         for kb in range(2):
@@ -203,8 +192,8 @@ def softmax_list(V, par, masked, u):
                     for kk in (k, k + 1):
                         out.append((f"v_cvt_pk_bf16_f32 {V.r('p', 8 * p + kk)}, v{S + 2 * kk}, "
                                     f"v{S + 2 * kk + 1}", COST["cvt"], gk[kb]))
-        return [it for it in out if not DROP & kinds.get(it[0].split()[0], 0)]
-    if CHAINS == 1 and not LAG1:
+        return out
+    if CHAINS == 1:
         for kb in range(2):
             for j in range(2):
                 p = 2 * kb + j
@@ -222,7 +211,7 @@ def softmax_list(V, par, masked, u):
                         out.append((f"v_add_f32 {ps}, {ps}, v{b}", COST["add"], 0))
                     out.append((f"v_cvt_pk_bf16_f32 {V.r('p', 8 * p + k)}, v{a}, v{b}",
                                 COST["cvt"], gk[kb]))
-        return [it for it in out if not DROP & kinds.get(it[0].split()[0], 0)]
+        return out
     # the tile's 64 scores in slot order; E = exp, A = accumulate (4 scores behind), C = cvt
     seq = []
     for kb in range(2):
@@ -252,26 +241,7 @@ def softmax_list(V, par, masked, u):
                 out.append((f"v_cvt_pk_bf16_f32 {V.r('p', 8 * p + k)}, v{S + r - 1}, v{S + r}",
                             COST["cvt"], gk[kb]))
     # combine the accumulators of each query block into ps
-    out += combine_list(V)
-    return [it for it in out if not DROP & kinds.get(it[0].split()[0], 0)]
-
-
-def combine_list(V):
-    """The CHAINS row-sum accumulators of each query block into ps (a pairwise tree)."""
-    out = []
-    if CHAINS == 1:
-        return [(f"v_mov_b32 {V.r('ps', j)}, {V.r('c', 4 * j)}", COST["add"], 0)
-                for j in range(2)]
-    step = 1
-    while step < CHAINS:
-        last = 2 * step >= CHAINS
-        for a in range(0, CHAINS, 2 * step):
-            for j in range(2):
-                dst = V.r("ps", j) if last else V.r("c", 4 * j + a)
-                out.append((f"v_add_f32 {dst}, {V.r('c', 4 * j + a)}, "
-                            f"{V.r('c', 4 * j + a + step)}", COST["add"], 0))
-        step *= 2
-    return out
+    return out + combine_list(V, CHAINS)
 
 
 def mask_list(V, S, masked, u, kb):
@@ -284,87 +254,34 @@ def mask_list(V, S, masked, u, kb):
     return out
 
 
-def place(items, ngaps):
-    """Greedy list schedule: gap g takes, in list order, the instructions whose earliest gap
-    has come, until the gap's share of the total cost is used; an instruction held back by
-    its earliest gap lets the later ones pass (only P^T writes are held back)."""
-    total = sum(c for _, c, _ in items)
-    per = total / ngaps
-    slots = [[] for _ in range(ngaps)]
-    done = [False] * len(items)
-    budget = 0.0
-    for g in range(ngaps):
-        budget += per
-        last = g == ngaps - 1
-        for k, (text, cost, early) in enumerate(items):
-            if done[k] or early > g:
-                continue
-            if not last and cost > budget + 1e-9:
-                break
-            slots[g].append(text)
-            budget -= cost
-            done[k] = True
-    assert all(done)
-    return slots
-
-
 # ------------------------------------------------------------------ prologue
 def prologue(st: Stream, V, A):
     e, r = st.emit, st.raw
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx8 s[32:39], {S_KARG}, 0x40")
     r(f"s_load_dwordx4 s[40:43], {S_KARG}, 0x60")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")  # first lane's id = 64 * wave
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
-    r("s_getpc_b64 s[68:69]")
-    r("s_add_u32 s68, s68, vd_attn_dq_lanes@rel32@lo+4")  # the dQ kernel's lane table
-    r("s_addc_u32 s69, s69, vd_attn_dq_lanes@rel32@hi+12")
-    # rare-path entry points: S_TGT + 2 v = .Lfwd_rare{v}
-    r(f"s_getpc_b64 s[{S_TGT}:{S_TGT + 1}]")
-    st.label(".Lfwd_pc")
-    for v in (3, 2, 1, 0):
-        r(f"s_add_u32 s{S_TGT + 2 * v}, s{S_TGT}, .Lfwd_rare{v}-.Lfwd_pc")
-        r(f"s_addc_u32 s{S_TGT + 2 * v + 1}, s{S_TGT + 1}, 0")
+    wave_and_table(st, V, S_WAVE, S_TAB, "vd_attn_dq_lanes")  # the dQ kernel's lane table
+    rare_targets(st, S_TGT, "fwd")
     r("s_waitcnt lgkmcnt(0)")
     # seq = wgz * groups + wgy ; base = wgz * bs + wgy * gs ; obase likewise (bytes, 64-bit)
     r(f"s_mul_i32 s70, {S_WGZ}, s29")
     r(f"s_add_u32 s70, s70, {S_WGY}")
-
-    def mad64(dlo, dhi, a, blo, bhi, t):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {t}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {t}")
-
-    mad64("s72", "s73", S_WGZ, "s30", "s31", "s71")
-    mad64("s76", "s77", S_WGY, "s32", "s33", "s71")
-    r("s_add_u32 s72, s72, s76")
-    r("s_addc_u32 s73, s73, s77")
-    mad64("s74", "s75", S_WGZ, "s34", "s35", "s71")
-    mad64("s76", "s77", S_WGY, "s36", "s37", "s71")
-    r("s_add_u32 s74, s74, s76")
-    r("s_addc_u32 s75, s75, s77")
-
-    def rsrc(dst, plo, phi, blo, bhi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {blo}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {bhi}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
-    rsrc(RQ, "s16", "s17", "s72", "s73", "s39")
-    rsrc(RK, "s18", "s19", "s72", "s73", "s39")
-    rsrc(RV, "s20", "s21", "s72", "s73", "s39")
-    rsrc(RO, "s22", "s23", "s74", "s75", "s40")
+    mad64(st, "s72", "s73", S_WGZ, "s30", "s31", "s71")
+    mad64(st, "s76", "s77", S_WGY, "s32", "s33", "s71")
+    add64(st, "s72", "s73", "s76", "s77")
+    mad64(st, "s74", "s75", S_WGZ, "s34", "s35", "s71")
+    mad64(st, "s76", "s77", S_WGY, "s36", "s37", "s71")
+    add64(st, "s74", "s75", "s76", "s77")
+    rsrc(st, RQ, "s16", "s17", "s39", ("s72", "s73"))
+    rsrc(st, RK, "s18", "s19", "s39", ("s72", "s73"))
+    rsrc(st, RV, "s20", "s21", "s39", ("s72", "s73"))
+    rsrc(st, RO, "s22", "s23", "s40", ("s74", "s75"))
     # lse row: seq * n * 4 bytes, n * 4 bytes long
     r("s_mul_i32 s76, s70, s26")
     r("s_mul_hi_u32 s77, s70, s26")
     r("s_lshl_b64 s[76:77], s[76:77], 2")
     r("s_lshl_b32 s71, s26, 2")
-    rsrc(RL, "s24", "s25", "s76", "s77", "s71")
+    rsrc(st, RL, "s24", "s25", "s71", ("s76", "s77"))
     # q0 = wgx * 256 + wave * 64 ; M0 base of this wave's DMA pieces = wave * 2048
     r(f"s_lshl_b32 {S_Q0}, {S_WGX}, 8")
     r(f"s_lshl_b32 s71, {S_WAVE}, 6")
@@ -401,14 +318,7 @@ def prologue(st: Stream, V, A):
     e(f"v_sub_u32 {V.r('klim')}, s43, {t1}")
     r("s_waitcnt vmcnt(0)")
     # Q' = bf16(Q * scale * log2 e), per bf16 element (attention.hip RowFrag::scale)
-    for w in range(32):
-        x = f"v{qv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s38, {t0}")
-        e(f"v_mul_f32 {t1}, s38, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('qf', w)}, {x}")
+    scale_bf16(st, qv, 32, "s38", t0, t1, lambda w: A.r("qf", w))
     for k in range(4):
         e(f"v_add_u32 {V.r('rowhi', k)}, {HI:#x}, {V.r('rowoff', k)}")
         e(f"v_add_u32 {V.r('trhi', k)}, {HI:#x}, {V.r('troff', k)}")
@@ -451,7 +361,7 @@ def prologue(st: Stream, V, A):
         for k in range(32):
             e(f"v_accvgpr_write_b32 {A.r('lsum', k)}, 0")
     for t in range(PD):
-        dma_tile(st, V, t)
+        dma_issue(st, *dma_ops(V, t))
 
 
 def dma_ops(V, stage):
@@ -463,16 +373,6 @@ def dma_ops(V, stage):
                         f"buffer_load_dwordx4 v{d0 + i}, {rs}, 0 offen lds"))
     adv = [f"v_add_u32 v{d0 + i}, s41, v{d0 + i}" for i in range(2)]
     return ops, adv
-
-
-def dma_tile(st: Stream, V, stage):
-    ops, adv = dma_ops(V, stage)
-    for m0, ld in ops:
-        st.raw(m0)
-        st.raw("s_nop 0")
-        st.emit(ld)
-    for a in adv:
-        st.emit(a)
 
 
 # ------------------------------------------------------------------ one body
@@ -491,8 +391,6 @@ def emit_check(st: Stream, V, A, u, masked, tag, msum):
     if CHECK_NOP:
         st.raw(f"s_nop {CHECK_NOP}")
     st.raw(f"s_cbranch_vccz .Lfwd_ok{tag}")
-    if NORARE:
-        st.raw(f"s_branch .Lfwd_ok{tag}")
     st.raw(f"s_mov_b32 {S_ST}, {u * STAGE}")
     st.raw(f"s_mov_b32 {S_ST1}, {kst * STAGE}")
     st.raw(f"s_mov_b32 {S_KB}, {64 * u}")
@@ -510,23 +408,11 @@ def emit_body(st: Stream, V, A, u, masked, tag, prev=None):
     st.comment(f"---- body, stage {u}{' (masked)' if masked else ''}")
     if MSUM:
         return emit_body_msum(st, V, A, u, masked, tag, prev)
-    if not BAR2:
-        st.raw(f"s_waitcnt vmcnt({(PD - 2) * 4}) lgkmcnt(0)")  # tile t+1 landed
-        st.raw("s_barrier")
-    elif u % 2 == 0:
-        st.raw(f"s_waitcnt vmcnt({(PD - 3) * 4}) lgkmcnt(0)")  # tiles t+1, t+2 landed
-        st.raw("s_barrier")
-    else:
-        st.raw("s_waitcnt lgkmcnt(0)")
+    st.raw(f"s_waitcnt vmcnt({(PD - 2) * 4}) lgkmcnt(0)")  # tile t+1 landed
+    st.raw("s_barrier")
     st.flush_lds()
-    if GSGS:
-        mf = (g_mfmas(V, A, 0) + s_mfmas(V, A, 1 - par, 0) + g_mfmas(V, A, 1)
-              + s_mfmas(V, A, 1 - par, 1))
-        rslots = (0, 8, 16, 24)
-    else:
-        mf = (g_mfmas(V, A, 0) + g_mfmas(V, A, 1) + s_mfmas(V, A, 1 - par, 0)
-              + s_mfmas(V, A, 1 - par, 1))
-        rslots = (2, 8, 12, 16)
+    mf = (g_mfmas(V, A, 0) + g_mfmas(V, A, 1) + s_mfmas(V, A, 1 - par, 0)
+          + s_mfmas(V, A, 1 - par, 1))
     nm = len(mf)
     reads = {}
 
@@ -535,24 +421,14 @@ def emit_body(st: Stream, V, A, u, masked, tag, prev=None):
             reads.setdefault(slot0 + k // per, []).append(item)
 
     kst = (u + 1) % NST
-    if not DROP & 8:
-        put(rslots[0], k_reads(V, A, kst, 0))  # K(t+1) rows, key block 0
-        put(rslots[1], tr_reads(V, A, u, 0))   # V(t)^T, for G(t) in the next body
-        put(rslots[2], k_reads(V, A, kst, 1))
-        put(rslots[3], tr_reads(V, A, u, 1))
+    put(2, k_reads(V, A, kst, 0))  # K(t+1) rows, key block 0
+    put(8, tr_reads(V, A, u, 0))   # V(t)^T, for G(t) in the next body
+    put(12, k_reads(V, A, kst, 1))
+    put(16, tr_reads(V, A, u, 1))
     ops, adv = dma_ops(V, (u + PD) % NST)
-    slots4 = ((4, 12, 20, 28), (1, 9, 17, 25), (6, 14, 22, 30), (0, 8, 16, 24))[DMAS]
-    dma_at = {} if DROP & 16 else {g: i for i, g in enumerate(slots4)}
     valu = place(softmax_list(V, par, masked, u), nm)
     for g in range(nm):
-        if g in dma_at:
-            m0, ld = ops[dma_at[g]]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if dma_at[g] == 3:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, DMA_AT, ops, adv)
         for text, rid in reads.get(g, []):
             st.emit(text, lds_id=rid)
         for text in valu[g]:
@@ -580,11 +456,11 @@ def emit_body_msum(st: Stream, V, A, u, masked, tag, prev):
         # softmax over gaps 0..31 as in the adds body
         mf = (g_mfmas(V, A, 0) + g_mfmas(V, A, 1) + s_mfmas(V, A, 1 - par, 0)
               + s_mfmas(V, A, 1 - par, 1) + sum16_mfmas(V, A))
-        rslots, dma_at, ngap = (2, 8, 12, 16), {4: 0, 12: 1, 20: 2, 28: 3}, 32
+        rslots, dma_at, ngap = (2, 8, 12, 16), DMA_AT, 32
     else:
         mf = (g_mfmas(V, A, 0) + g_mfmas(V, A, 1) + s_mfmas(V, A, 1 - par, 0)
               + sum_mfmas(V, A) + s_mfmas(V, A, 1 - par, 1))
-        rslots, dma_at, ngap = (2, 24, 12, 32), {4: 0, 12: 1, 34: 2, 38: 3}, 24
+        rslots, dma_at, ngap = (2, 24, 12, 32), (4, 12, 34, 38), 24
     nm = len(mf)
     reads = {}
 
@@ -593,22 +469,14 @@ def emit_body_msum(st: Stream, V, A, u, masked, tag, prev):
             reads.setdefault(slot0 + k // per, []).append(item)
 
     kst = (u + 1) % NST
-    if not DROP & 8:
-        put(rslots[0], k_reads(V, A, kst, 0))   # K(t+1) rows kb0
-        put(rslots[2], k_reads(V, A, kst, 1))   # kb1
-        put(rslots[1], tr_reads(V, A, u, 0))    # V(t)^T for G(t) in the next body
-        put(rslots[3], tr_reads(V, A, u, 1))
+    put(rslots[0], k_reads(V, A, kst, 0))   # K(t+1) rows kb0
+    put(rslots[2], k_reads(V, A, kst, 1))   # kb1
+    put(rslots[1], tr_reads(V, A, u, 0))    # V(t)^T for G(t) in the next body
+    put(rslots[3], tr_reads(V, A, u, 1))
     ops, adv = dma_ops(V, (u + PD) % NST)
     valu = place(softmax_list(V, par, masked, u), ngap)
     for g in range(nm):
-        if g in dma_at:
-            m0, ld = ops[dma_at[g]]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if dma_at[g] == 3:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, dma_at, ops, adv)
         for text, rid in reads.get(g, []):
             st.emit(text, lds_id=rid)
         if g < ngap:
@@ -674,7 +542,7 @@ def rare_path(V, A, par, masked):
     st = Stream()
     e, r = st.emit, st.raw
     st.label(f".Lfwd_rare{2 * int(masked) + par}")
-    r("s_add_u32 s79, s79, 1")  # rare-path count (read by diagnostic probes only)
+    r("s_add_u32 s79, s79, 1")  # rare-path count (diagnostic; no shipped code reads it)
     r("s_nop 15")
     r("s_nop 15")
     r("s_waitcnt lgkmcnt(0)")
@@ -785,64 +653,27 @@ def rare_path(V, A, par, masked):
     return st
 
 
-def emit_stamp(st: Stream, V):
-    """STAMP builds: lane 0 of each wave stores (loop cycles, loop realtime ticks) at
-    dbg[(wgx * 4 + wave) * 2] (dbg pointer at kernarg offset KARG)."""
-    r = st.raw
-    r("s_memtime s[94:95]")
-    r("s_memrealtime s[72:73]")
-    r(f"s_load_dwordx2 s[74:75], {S_KARG}, {KARG}")
-    r("s_waitcnt lgkmcnt(0)")
-    r("s_sub_u32 s94, s94, s90")
-    r("s_sub_u32 s72, s72, s92")
-    t0, t1, t2 = V.r("tmp", 0), V.r("tmp", 1), V.r("tmp", 2)
-    r(f"s_lshl_b32 s70, {S_WGX}, 2")
-    r(f"s_add_u32 s70, s70, {S_WAVE}")
-    r("s_lshl_b32 s70, s70, 3")
-    r(f"v_mov_b32 {t0}, s70")
-    r(f"v_mov_b32 {t1}, s94")
-    r(f"v_mov_b32 {t2}, s72")
-    r("s_mov_b64 exec, 1")
-    r(f"global_store_dword {t0}, {t1}, s[74:75]")
-    r(f"global_store_dword {t0}, {t2}, s[74:75] offset:4")
-    r("s_mov_b64 exec, -1")
-    r("s_waitcnt vmcnt(0)")
-
-
-def gen_fwd(probe=None):
+def gen_fwd():
     V, A = regs()
     assert V.next <= 256 and A.next <= 256, (V.next, A.next)
     st = Stream()
     prologue(st, V, A)
-    if probe and probe[0] == "prologue":
-        from gen_attn_asm import emit_probe
-        emit_probe(st, probe[1], KARG, tmp=(V.r("tmp", 0), V.r("tmp", 1)))
-    if STAMP:
-        st.raw("s_memtime s[90:91]")
-        st.raw("s_memrealtime s[92:93]")
     st.label(".Lfwd_loop")
     for u in range(NST):
         emit_body(st, V, A, u, False, f"{u}", prev=((u - 1) % NST, False))
-    st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Lfwd_loop")
+    loop_tail(st, S_ITER, ".Lfwd_loop")
     for u in range(NST):
         emit_body(st, V, A, u, True, f"m{u}", prev=((u - 1) % NST, u > 0))
     if MSUM:  # the last tile's check
         st.raw("s_waitcnt lgkmcnt(0)")
         emit_check(st, V, A, NST - 1, True, "last", True)
     emit_tail(st, V, A)
-    if STAMP:
-        emit_stamp(st, V)
-    if probe and probe[0] == "loop":
-        from gen_attn_asm import emit_probe
-        emit_probe(st, probe[1], KARG, tmp=(V.r("tmp", 0), V.r("tmp", 1)))
     epilogue(st, V, A)
     body = st.text() + "\ts_endpgm\n"
     for masked in (False, True):
         for par in range(2):
             body += rare_path(V, A, par, masked).text()
     k = kernel_text("vd_attn_fwd_d64", body, vgprs=V.next, agprs=A.next, sgprs=96,
-                    lds_bytes=NST * STAGE, kernarg_bytes=KARG + (8 if probe or STAMP else 0),
+                    lds_bytes=NST * STAGE, kernarg_bytes=KARG,
                     wg_size=64 * NW)
     return k, st

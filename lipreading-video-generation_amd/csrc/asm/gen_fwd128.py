@@ -21,7 +21,9 @@ the per-lane offsets.  An iteration is 8 bodies (256 keys); keys past the end ar
 """
 from __future__ import annotations
 
-from asmgen import Regs, Stream, kernel_text
+from asmgen import (COST, HI, Regs, Stream, add64, combine_list, dma_at_gap, dma_issue,
+                    frag_offsets, kernel_text, lane_table_data, lds, loop_tail, mad64, place,
+                    rare_targets, rsrc, scale_bf16, swz, wave_and_table)
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4
@@ -32,11 +34,12 @@ PD = 4                 # prefetch distance (tiles)
 STAGE = 16384          # K tile | V tile (32 x 128 bf16 each)
 VOFF = 8192
 KARG = 112             # AsmFwdArgs (vd_asm.h); tile_bytes = 32 rows here
-HI = 65536
 NINF, PINF = "0xff800000", "0x7f800000"
 CHECK_NOP = 3
 CHAINS = 4
-DMAS = 0               # LDS-DMA slots of a body (A/B): 0 {4,12,20,28} 1 {1,9,17,25} 2 {6,14,22,30}
+DMA_AT = (4, 12, 20, 28)   # LDS-DMA gaps of a body.  Measured and removed: {1,9,17,25} and
+                       # {6,14,22,30} (DMAS), 1.77 / 1.73 vs 1.75-1.79 ms at N = 65536, within the
+                       # run's spread (profiles/r03_ab_fwd_knobs2.txt)
 KSLOT = 0              # first gap of the K(t+1) row reads (one per gap)
 
 S_KARG = "s[0:1]"
@@ -46,15 +49,6 @@ S_WAVE, S_Q0, S_M0, S_ITER, S_TAB = "s64", "s65", "s66", "s67", "s[68:69]"
 S_ST, S_ST1, S_KB, S_RET, S_TGT = "s76", "s77", "s78", "s[80:81]", 82
 
 
-def swz(r):
-    """attention.hip swz_row<128>."""
-    return ((r & 3) << 2) | ((r >> 2) & 3)
-
-
-def toff_bytes(r, c):
-    return 2 * (r * D + (((c >> 3) ^ swz(r)) << 3) + (c & 7))
-
-
 def lane_table():
     """tab[wave][lane][32] u32: 0-7 K row-fragment offsets (k-step s), 8-15 V^T
     transposed-fragment offsets (2 i + hi), 16-17 DMA rows of the wave's 2 pieces of a
@@ -62,22 +56,13 @@ def lane_table():
     out = []
     for w in range(NW):
         for lane in range(64):
-            r, hh = lane & 31, lane >> 5
-            row = [toff_bytes(r, 16 * s + 8 * hh) for s in range(8)]
-            g, fr = lane >> 4, lane & 15
-            q4, p4 = fr >> 2, fr & 3
-            tr = []
-            for i in range(4):
-                col = 32 * i + 16 * (g & 1) + 4 * p4
-                kr = 4 * (g >> 1) + q4
-                tr += [toff_bytes(kr, col), toff_bytes(kr + 8, col)]
             drow, dch = [], []
             for i in range(2):
                 gi = w * 2 + i
                 rr = gi * 4 + lane // 16
                 drow.append(rr)
-                dch.append(((lane % 16) ^ swz(rr)) * 16)
-            out.append(row + tr + drow + dch + [0] * 12)
+                dch.append(((lane % 16) ^ swz(D, rr)) * 16)
+            out.append(frag_offsets(D, lane, 8, 4) + drow + dch + [0] * 12)
     return out
 
 
@@ -101,12 +86,6 @@ def regs():
 
 def sblk(V, par, j):
     return V.r(f"s{par}", 16 * j, 16)
-
-
-def lds(V, name, k, off):
-    if off >= HI:
-        return V.r({"rowoff": "rowhi", "troff": "trhi"}[name], k), off - HI
-    return V.r(name, k), off
 
 
 def k_reads(V, A, stage):
@@ -151,9 +130,6 @@ def s_mfmas(V, A, par, zero_c=False):
 
 
 # ------------------------------------------------------------------ softmax stream
-COST = {"exp": 8.0, "add": 4.0, "cvt": 4.5, "cmp": 4.0, "cnd": 4.0}
-
-
 def softmax_list(V, par, masked, u):
     """[(text, cost, earliest gap)] of tile t's softmax: per score v_exp_f32, an add into one
     of CHAINS row-sum accumulators of its query block 4 scores behind, half a cvt; the cvt
@@ -181,26 +157,7 @@ def softmax_list(V, par, masked, u):
                 k = r // 2
                 out.append((f"v_cvt_pk_bf16_f32 {V.r('p', 8 * j + k)}, v{S + r - 1}, v{S + r}",
                             COST["cvt"], 16 + 2 * (k // 4) + j))
-    out += combine_list(V)
-    return out
-
-
-def combine_list(V):
-    """The CHAINS row-sum accumulators of each query block into ps (a pairwise tree)."""
-    out = []
-    if CHAINS == 1:
-        return [(f"v_mov_b32 {V.r('ps', j)}, {V.r('c', 4 * j)}", COST["add"], 0)
-                for j in range(2)]
-    step = 1
-    while step < CHAINS:
-        last = 2 * step >= CHAINS
-        for a in range(0, CHAINS, 2 * step):
-            for j in range(2):
-                dst = V.r("ps", j) if last else V.r("c", 4 * j + a)
-                out.append((f"v_add_f32 {dst}, {V.r('c', 4 * j + a)}, "
-                            f"{V.r('c', 4 * j + a + step)}", COST["add"], 0))
-        step *= 2
-    return out
+    return out + combine_list(V, CHAINS)
 
 
 def mask_list(V, S, u):
@@ -213,82 +170,32 @@ def mask_list(V, S, u):
     return out
 
 
-def place(items, ngaps):
-    """Greedy list schedule by cost (gen_fwd.place)."""
-    total = sum(c for _, c, _ in items)
-    per = total / ngaps
-    slots = [[] for _ in range(ngaps)]
-    done = [False] * len(items)
-    budget = 0.0
-    for g in range(ngaps):
-        budget += per
-        last = g == ngaps - 1
-        for k, (text, cost, early) in enumerate(items):
-            if done[k] or early > g:
-                continue
-            if not last and cost > budget + 1e-9:
-                break
-            slots[g].append(text)
-            budget -= cost
-            done[k] = True
-    assert all(done)
-    return slots
-
-
 # ------------------------------------------------------------------ prologue
 def prologue(st: Stream, V, A):
     e, r = st.emit, st.raw
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx8 s[32:39], {S_KARG}, 0x40")
     r(f"s_load_dwordx4 s[40:43], {S_KARG}, 0x60")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
-    r("s_getpc_b64 s[68:69]")
-    r("s_add_u32 s68, s68, vd_attn_fwd128_lanes@rel32@lo+4")
-    r("s_addc_u32 s69, s69, vd_attn_fwd128_lanes@rel32@hi+12")
-    r(f"s_getpc_b64 s[{S_TGT}:{S_TGT + 1}]")
-    st.label(".Lfwd128_pc")
-    for v in (3, 2, 1, 0):
-        r(f"s_add_u32 s{S_TGT + 2 * v}, s{S_TGT}, .Lfwd128_rare{v}-.Lfwd128_pc")
-        r(f"s_addc_u32 s{S_TGT + 2 * v + 1}, s{S_TGT + 1}, 0")
+    wave_and_table(st, V, S_WAVE, S_TAB, "vd_attn_fwd128_lanes")
+    rare_targets(st, S_TGT, "fwd128")
     r("s_waitcnt lgkmcnt(0)")
     r(f"s_mul_i32 s70, {S_WGZ}, s29")
     r(f"s_add_u32 s70, s70, {S_WGY}")
-
-    def mad64(dlo, dhi, a, blo, bhi, t):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {t}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {t}")
-
-    mad64("s72", "s73", S_WGZ, "s30", "s31", "s71")
-    mad64("s76", "s77", S_WGY, "s32", "s33", "s71")
-    r("s_add_u32 s72, s72, s76")
-    r("s_addc_u32 s73, s73, s77")
-    mad64("s74", "s75", S_WGZ, "s34", "s35", "s71")
-    mad64("s76", "s77", S_WGY, "s36", "s37", "s71")
-    r("s_add_u32 s74, s74, s76")
-    r("s_addc_u32 s75, s75, s77")
-
-    def rsrc(dst, plo, phi, blo, bhi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {blo}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {bhi}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
-    rsrc(RQ, "s16", "s17", "s72", "s73", "s39")
-    rsrc(RK, "s18", "s19", "s72", "s73", "s39")
-    rsrc(RV, "s20", "s21", "s72", "s73", "s39")
-    rsrc(RO, "s22", "s23", "s74", "s75", "s40")
+    mad64(st, "s72", "s73", S_WGZ, "s30", "s31", "s71")
+    mad64(st, "s76", "s77", S_WGY, "s32", "s33", "s71")
+    add64(st, "s72", "s73", "s76", "s77")
+    mad64(st, "s74", "s75", S_WGZ, "s34", "s35", "s71")
+    mad64(st, "s76", "s77", S_WGY, "s36", "s37", "s71")
+    add64(st, "s74", "s75", "s76", "s77")
+    rsrc(st, RQ, "s16", "s17", "s39", ("s72", "s73"))
+    rsrc(st, RK, "s18", "s19", "s39", ("s72", "s73"))
+    rsrc(st, RV, "s20", "s21", "s39", ("s72", "s73"))
+    rsrc(st, RO, "s22", "s23", "s40", ("s74", "s75"))
     r("s_mul_i32 s76, s70, s26")
     r("s_mul_hi_u32 s77, s70, s26")
     r("s_lshl_b64 s[76:77], s[76:77], 2")
     r("s_lshl_b32 s71, s26, 2")
-    rsrc(RL, "s24", "s25", "s76", "s77", "s71")
+    rsrc(st, RL, "s24", "s25", "s71", ("s76", "s77"))
     # q0 = wgx * 256 + wave * 64 ; M0 base of this wave's DMA pieces = wave * 2048
     r(f"s_lshl_b32 {S_Q0}, {S_WGX}, 8")
     r(f"s_lshl_b32 s71, {S_WAVE}, 6")
@@ -326,14 +233,7 @@ def prologue(st: Stream, V, A):
     e(f"v_lshrrev_b32 {t1}, 2, {hh16}")
     e(f"v_sub_u32 {V.r('klim')}, s43, {t1}")
     r("s_waitcnt vmcnt(0)")
-    for w in range(64):
-        x = f"v{qv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s38, {t0}")
-        e(f"v_mul_f32 {t1}, s38, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('qf', w)}, {x}")
+    scale_bf16(st, qv, 64, "s38", t0, t1, lambda w: A.r("qf", w))
     for k in range(8):
         e(f"v_add_u32 {V.r('rowhi', k)}, {HI:#x}, {V.r('rowoff', k)}")
         e(f"v_add_u32 {V.r('trhi', k)}, {HI:#x}, {V.r('troff', k)}")
@@ -357,13 +257,7 @@ def prologue(st: Stream, V, A):
         e(f"v_mov_b32 {V.r('ps', j)}, 0")
     e(f"v_mov_b32 {V.r('ninf')}, {NINF}")
     for t in range(PD):
-        ops, adv = dma_ops(V, t)
-        for m0, ld in ops:
-            r(m0)
-            r("s_nop 0")
-            e(ld)
-        for a in adv:
-            e(a)
+        dma_issue(st, *dma_ops(V, t))
 
 
 def dma_ops(V, stage):
@@ -396,17 +290,9 @@ def emit_body(st: Stream, V, A, u, masked, tag):
     put(KSLOT, k_reads(V, A, kst), 1)  # K(t+1) rows: gaps 0..7, read by S(t+1) from gap 16
     put(16, tr_reads(V, A, u), 2)     # V(t)^T for G(t) in the next body: gaps 16..23
     ops, adv = dma_ops(V, (u + PD) % NST)
-    dma_at = {g: i for i, g in enumerate(((4, 12, 20, 28), (1, 9, 17, 25), (6, 14, 22, 30))[DMAS])}
     valu = place(softmax_list(V, par, masked, u), nm)
     for g in range(nm):
-        if g in dma_at:
-            m0, ld = ops[dma_at[g]]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if dma_at[g] == 3:
-                for a in adv:
-                    st.emit(a)
+        dma_at_gap(st, g, DMA_AT, ops, adv)
         for text, rid in reads.get(g, []):
             st.emit(text, lds_id=rid)
         for text in valu[g]:
@@ -481,7 +367,7 @@ def rare_path(V, A, par, masked):
     st = Stream()
     e, r = st.emit, st.raw
     st.label(f".Lfwd128_rare{2 * int(masked) + par}")
-    r("s_add_u32 s79, s79, 1")  # rare-path count (diagnostic probes only)
+    r("s_add_u32 s79, s79, 1")  # rare-path count (diagnostic; no shipped code reads it)
     r("s_nop 15")
     r("s_nop 15")
     r("s_waitcnt lgkmcnt(0)")
@@ -579,9 +465,7 @@ def gen_fwd128():
     st.label(".Lfwd128_loop")
     for u in range(NST):
         emit_body(st, V, A, u, False, f"{u}")
-    st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Lfwd128_loop")
+    loop_tail(st, S_ITER, ".Lfwd128_loop")
     for u in range(NST):
         emit_body(st, V, A, u, True, f"m{u}")
     emit_tail(st, V, A)
@@ -592,7 +476,4 @@ def gen_fwd128():
             body += rare_path(V, A, par, masked).text()
     k = kernel_text("vd_attn_fwd_d128", body, vgprs=V.next, agprs=A.next, sgprs=96,
                     lds_bytes=NST * STAGE, kernarg_bytes=KARG, wg_size=64 * NW)
-    data = "\n.rodata\n.p2align 8\nvd_attn_fwd128_lanes:\n"
-    for row in lane_table():
-        data += "\t.long " + ", ".join(str(x) for x in row) + "\n"
-    return k, data, st
+    return k, lane_table_data("vd_attn_fwd128_lanes", lane_table()), st

@@ -26,15 +26,15 @@ alone is 128 workgroups, half the chip.
 """
 from __future__ import annotations
 
-from asmgen import Regs, Stream, kernel_text
-from gen_d256 import KTILE, VBASE, swz, toff_bytes  # noqa: F401  (lane table: gen_d256)
+from asmgen import (COST, HI, Regs, Stream, add64, dma_at_gap, dma_issue, kernel_text, loop_tail,
+                    mad64, place, rare_targets, rsrc, scale_bf16, wave_and_table)
+from gen_d256 import KTILE, VBASE  # (the lane table is gen_d256's too)
 
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NW = 4
 D = 256
 KT = 32
 NST = 4
-HI = 65536
 KARG = 160               # AsmFwd256Args (vd_asm.h)
 RING = 8                 # K row-fragment ring slots
 TRING = 8                # V^T fragment ring slots (lo 2 + hi 2)
@@ -63,6 +63,7 @@ S_ST, S_ST1, S_KB = "s84", "s85", "s86"
 S_RET = "s[88:89]"
 S_TGT = 90                        # s90..s97: the 4 rare-path entry points
 S_T0, S_T1, S_T2, S_T3 = "s98", "s99", "s100", "s101"
+S_T01 = (S_T0, S_T1)              # the byte offset the prologue's buffer resources are based at
 
 
 def regs():
@@ -125,9 +126,6 @@ def g_mfmas(V, A, deps=True):
 
 
 # ------------------------------------------------------------------ softmax stream
-COST = {"exp": 8.0, "add": 4.0, "cvt": 4.5, "cmp": 4.0, "cnd": 4.0}
-
-
 def mask_list(V, S, u):
     """Keys >= the split's end to -inf in the score block S of the tile in stage u of the last
     iteration (klim = keys in the last iteration - 4 hh)."""
@@ -168,41 +166,14 @@ def softmax_list(V, par, masked_u):
     return out
 
 
-def place(items, ngaps):
-    """Greedy list schedule by cost over ngaps gaps (gen_fwd.place without earliest gaps)."""
-    total = sum(c for _, c in items)
-    per = total / ngaps
-    slots = [[] for _ in range(ngaps)]
-    k = 0
-    budget = 0.0
-    for g in range(ngaps):
-        budget += per
-        while k < len(items) and (g == ngaps - 1 or items[k][1] <= budget + 1e-9):
-            slots[g].append(items[k][0])
-            budget -= items[k][1]
-            k += 1
-    assert k == len(items)
-    return slots
-
-
 # ------------------------------------------------------------------ prologue
 def prologue(st: Stream, V, A):
     e, r = st.emit, st.raw
     r(f"s_load_dwordx16 s[16:31], {S_KARG}, 0x0")
     r(f"s_load_dwordx16 s[32:47], {S_KARG}, 0x40")
     r(f"s_load_dwordx8 s[48:55], {S_KARG}, 0x80")
-    e(f"v_and_b32 {V.r('lane')}, 63, {V.r('tid')}")
-    r(f"v_readfirstlane_b32 {S_WAVE}, {V.r('tid')}")
-    r("s_nop 1")
-    r(f"s_lshr_b32 {S_WAVE}, {S_WAVE}, 6")
-    r(f"s_getpc_b64 {S_TAB}")
-    r("s_add_u32 s6, s6, vd_attn_d256_lanes@rel32@lo+4")
-    r("s_addc_u32 s7, s7, vd_attn_d256_lanes@rel32@hi+12")
-    r(f"s_getpc_b64 s[{S_TGT}:{S_TGT + 1}]")
-    st.label(".Lfwd256_pc")
-    for v in (3, 2, 1, 0):
-        r(f"s_add_u32 s{S_TGT + 2 * v}, s{S_TGT}, .Lfwd256_rare{v}-.Lfwd256_pc")
-        r(f"s_addc_u32 s{S_TGT + 2 * v + 1}, s{S_TGT + 1}, 0")
+    wave_and_table(st, V, S_WAVE, S_TAB, "vd_attn_d256_lanes")
+    rare_targets(st, S_TGT, "fwd256")
     r("s_waitcnt lgkmcnt(0)")
     # grid.z = (sequence group z') << lsplit | split
     r(f"s_lshl_b32 {S_X}, 1, s47")
@@ -212,29 +183,11 @@ def prologue(st: Stream, V, A):
     r(f"s_mul_i32 {S_SEQ}, {S_ZS}, s29")
     r(f"s_add_u32 {S_SEQ}, {S_SEQ}, {S_WGY}")
 
-    def mad64(dlo, dhi, a, blo, bhi):
-        r(f"s_mul_i32 {dlo}, {a}, {blo}")
-        r(f"s_mul_hi_u32 {dhi}, {a}, {blo}")
-        r(f"s_mul_i32 {S_X}, {a}, {bhi}")
-        r(f"s_add_u32 {dhi}, {dhi}, {S_X}")
-
-    def add64():  # T0:T1 += T2:T3
-        r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
-        r(f"s_addc_u32 {S_T1}, {S_T1}, {S_T3}")
-
-    def rsrc(dst, plo, phi, nrec):
-        d0 = int(dst[2:].split(":")[0])
-        r(f"s_add_u32 s{d0}, {plo}, {S_T0}")
-        r(f"s_addc_u32 s{d0 + 1}, {phi}, {S_T1}")
-        r(f"s_and_b32 s{d0 + 1}, s{d0 + 1}, 0xffff")
-        r(f"s_mov_b32 s{d0 + 2}, {nrec}")
-        r(f"s_mov_b32 s{d0 + 3}, 0x20000")
-
     # q sequence base
-    mad64(S_T0, S_T1, S_ZS, "s30", "s31")
-    mad64(S_T2, S_T3, S_WGY, "s32", "s33")
-    add64()
-    rsrc(RQ, "s16", "s17", "s39")
+    mad64(st, S_T0, S_T1, S_ZS, "s30", "s31", S_X)
+    mad64(st, S_T2, S_T3, S_WGY, "s32", "s33", S_X)
+    add64(st, S_T0, S_T1, S_T2, S_T3)
+    rsrc(st, RQ, "s16", "s17", "s39", S_T01)
     # K / V: the split's keys [split * kps, +keys): base += split * kps * ts_bytes, range
     # (keys - 1) * ts_bytes + 512; S_Y0 = keys of the split (> 0: host)
     r(f"s_mul_i32 {S_T2}, {S_SPLIT}, s46")
@@ -247,8 +200,8 @@ def prologue(st: Stream, V, A):
     r(f"s_add_u32 {S_T0}, {S_T0}, {S_T2}")
     r(f"s_addc_u32 {S_T1}, {S_T1}, 0")
     r(f"s_mov_b32 {S_T3}, {S_X}")
-    rsrc(RK, "s18", "s19", S_T3)
-    rsrc(RV, "s20", "s21", S_T3)
+    rsrc(st, RK, "s18", "s19", S_T3, S_T01)
+    rsrc(st, RV, "s20", "s21", S_T3, S_T01)
     # iterations of 128 keys: S_Y1 = ceil(keys / 128); the loop runs S_Y1 - 1 of them, the
     # masked copy the last one (keys in it: keys - 128 (S_Y1 - 1))
     r(f"s_add_u32 {S_Y1}, {S_Y0}, 127")
@@ -261,13 +214,13 @@ def prologue(st: Stream, V, A):
     # else the bf16 O rows and the lse row of the sequence
     r("s_cmp_eq_u64 s[44:45], 0")
     r("s_cbranch_scc1 .Lfwd256_out_bf16")
-    mad64(S_T0, S_T1, S_SPLIT, "s48", "s49")
+    mad64(st, S_T0, S_T1, S_SPLIT, "s48", "s49", S_X)
     r(f"s_mul_i32 {S_T2}, {S_SEQ}, s26")
     r(f"s_mul_hi_u32 {S_T3}, {S_SEQ}, s26")
     r("s_lshl_b64 s[100:101], s[100:101], 10")
-    add64()
+    add64(st, S_T0, S_T1, S_T2, S_T3)
     r(f"s_lshl_b32 {S_X}, s26, 10")
-    rsrc(RO, "s44", "s45", S_X)
+    rsrc(st, RO, "s44", "s45", S_X, S_T01)
     r(f"s_mul_i32 {S_T0}, {S_SPLIT}, s52")
     r(f"s_mov_b32 {S_T1}, 0")
     r(f"s_add_u32 {S_T0}, {S_T0}, s50")
@@ -275,20 +228,20 @@ def prologue(st: Stream, V, A):
     r(f"s_mul_i32 {S_T2}, {S_SEQ}, s26")
     r(f"s_mul_hi_u32 {S_T3}, {S_SEQ}, s26")
     r("s_lshl_b64 s[100:101], s[100:101], 3")
-    add64()
+    add64(st, S_T0, S_T1, S_T2, S_T3)
     r(f"s_lshl_b32 {S_X}, s26, 3")
-    rsrc(RL, "s44", "s45", S_X)
+    rsrc(st, RL, "s44", "s45", S_X, S_T01)
     r("s_branch .Lfwd256_out_done")
     st.label(".Lfwd256_out_bf16")
-    mad64(S_T0, S_T1, S_ZS, "s34", "s35")
-    mad64(S_T2, S_T3, S_WGY, "s36", "s37")
-    add64()
-    rsrc(RO, "s22", "s23", "s40")
+    mad64(st, S_T0, S_T1, S_ZS, "s34", "s35", S_X)
+    mad64(st, S_T2, S_T3, S_WGY, "s36", "s37", S_X)
+    add64(st, S_T0, S_T1, S_T2, S_T3)
+    rsrc(st, RO, "s22", "s23", "s40", S_T01)
     r(f"s_mul_i32 {S_T0}, {S_SEQ}, s26")
     r(f"s_mul_hi_u32 {S_T1}, {S_SEQ}, s26")
     r("s_lshl_b64 s[98:99], s[98:99], 2")
     r(f"s_lshl_b32 {S_X}, s26, 2")
-    rsrc(RL, "s24", "s25", S_X)
+    rsrc(st, RL, "s24", "s25", S_X, S_T01)
     st.label(".Lfwd256_out_done")
     # q0 = wgx * 128 + wave * 32 ; M0 base of this wave's DMA pieces = wave * 4096
     r(f"s_lshl_b32 {S_Q0}, {S_WGX}, 7")
@@ -335,14 +288,7 @@ def prologue(st: Stream, V, A):
     e(f"v_sub_u32 {V.r('klim')}, {S_Y0}, {t1}")
     r("s_waitcnt vmcnt(0)")
     # Q' = bf16(Q * scale * log2 e)
-    for w in range(64):
-        x = f"v{qv + w}"
-        e(f"v_lshlrev_b32 {t0}, 16, {x}")
-        e(f"v_and_b32 {t1}, 0xffff0000, {x}")
-        e(f"v_mul_f32 {t0}, s38, {t0}")
-        e(f"v_mul_f32 {t1}, s38, {t1}")
-        e(f"v_cvt_pk_bf16_f32 {x}, {t0}, {t1}")
-        e(f"v_accvgpr_write_b32 {A.r('qf', w)}, {x}")
+    scale_bf16(st, qv, 64, "s38", t0, t1, lambda w: A.r("qf", w))
     # DMA source offsets of tile 0: row * ts_bytes + chunk * 16
     for i in range(4):
         e(f"v_mul_lo_u32 {V.r('dma', i)}, {V.r('dma', i)}, s27")
@@ -370,13 +316,7 @@ def prologue(st: Stream, V, A):
     e(f"v_mov_b32 {V.r('l')}, 0")
     e(f"v_mov_b32 {V.r('ninf')}, {NINF}")
     for t in range(2):
-        ops, adv = dma_ops(V, t)
-        for m0, ld in ops:
-            r(m0)
-            r("s_nop 0")
-            e(ld)
-        for a in adv:
-            e(a)
+        dma_issue(st, *dma_ops(V, t))
 
 
 def dma_ops(V, stage):
@@ -432,14 +372,8 @@ def emit_body(st: Stream, V, A, u, masked_soft, tag, dma=True):
     for g in range(32):
         if g == 16:
             emit_check(st, V, u, masked_soft, tag)
-        if dma and g in DMA_AT:
-            m0, ld = ops[DMA_AT.index(g)]
-            st.raw(m0)
-            st.raw("s_nop 0")
-            st.emit(ld)
-            if g == DMA_AT[-1]:
-                for a in adv:
-                    st.emit(a)
+        if dma:
+            dma_at_gap(st, g, DMA_AT, ops, adv)
         for text, rid in slots.get(g, []):
             st.emit(text, lds_id=rid)
         if g < 16:
@@ -617,9 +551,7 @@ def gen_fwd256():
     st.label(".Lfwd256_loop")
     for u in range(NST):
         emit_body(st, V, A, u, False, f"{u}")
-    st.raw(f"s_sub_u32 {S_ITER}, {S_ITER}, 1")
-    st.raw(f"s_cmp_lg_u32 {S_ITER}, 0")
-    st.raw("s_cbranch_scc1 .Lfwd256_loop")
+    loop_tail(st, S_ITER, ".Lfwd256_loop")
     st.label(".Lfwd256_last")
     for u in range(NST):
         emit_body(st, V, A, u, u > 0, f"m{u}")

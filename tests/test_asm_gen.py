@@ -182,3 +182,132 @@ def test_fwd_row_sum_mfma_variant(gens):
     text = st.text()
     assert text.count("v_mfma_f32_16x16x32_bf16") == 8 * 16
     assert text.count("v_add_f32") < 200  # the per-score adds are gone (l updates remain)
+
+
+# ------------------------------------------------------------------ shared generator helpers
+@pytest.fixture(scope="module")
+def asmgen(gens):
+    import asmgen as M
+    return M
+
+
+def _check_place(asmgen, items, ngaps):
+    """The scheduler's contract on one item list; returns the gaps."""
+    slots = asmgen.place(items, ngaps)
+    assert len(slots) == ngaps
+    texts = [it[0] for it in items]
+    assert len(set(texts)) == len(texts)
+    flat = [t for gap in slots for t in gap]
+    assert sorted(flat) == sorted(texts)                  # every item in exactly one gap
+    gap_of = {t: g for g, gap in enumerate(slots) for t in gap}
+    early = {it[0]: (it[2] if len(it) > 2 else 0) for it in items}
+    for t in texts:
+        assert gap_of[t] >= early[t], (t, gap_of[t], early[t])   # never before its earliest gap
+    for e in set(early.values()):                         # equal earliest gap: list order kept
+        same = [t for t in texts if early[t] == e]
+        assert [t for t in flat if early[t] == e] == same
+    return slots
+
+
+def test_place_hand_written_lists(asmgen):
+    # 2-tuples behave as earliest = 0; an even split fills each gap's share
+    two = [("a", 1.0), ("b", 1.0), ("c", 1.0), ("d", 1.0)]
+    assert _check_place(asmgen, two, 2) == [["a", "b"], ["c", "d"]]
+    assert _check_place(asmgen, [(t, c, 0) for t, c in two], 2) == [["a", "b"], ["c", "d"]]
+    # a held-back item (earliest gap 2) is overtaken by the two behind it and lands at gap 2
+    held = [("w", 1.0, 2), ("x", 1.0, 0), ("y", 1.0, 0), ("z", 1.0, 0)]
+    assert _check_place(asmgen, held, 4) == [["x"], ["y"], ["w"], ["z"]]
+    # list order within a gap's budget: "c" would fit gap 0 but does not pass "b"; the last
+    # gap absorbs the remainder, over its share
+    rest = [("a", 2.0), ("b", 5.0), ("c", 1.0)]
+    assert _check_place(asmgen, rest, 2) == [["a"], ["b", "c"]]
+    # equal earliest gaps keep list order, also behind items that passed them
+    eq = [("p0", 1.0, 1), ("p1", 1.0, 1), ("e", 1.0, 0), ("f", 1.0, 0)]
+    assert _check_place(asmgen, eq, 2) == [["e", "f"], ["p0", "p1"]]
+    # everything held back to the last gap
+    late = [("a", 1.0, 2), ("b", 3.0, 2), ("c", 1.0)]
+    assert _check_place(asmgen, late, 3) == [["c"], [], ["a", "b"]]
+    # mixed tuple shapes, one gap
+    assert _check_place(asmgen, [("a", 4.5, 0), ("b", 8.0)], 1) == [["a", "b"]]
+
+
+def test_place_on_a_real_softmax_list(gens, asmgen):
+    """The contract holds on the head_dim-64 forward's masked softmax list (P^T packs held
+    back to gaps 9 / 17) over its 32 gaps."""
+    _, F64, *_ = gens
+    V, _ = F64.regs()
+    items = F64.softmax_list(V, 0, True, 3)
+    items = [(f"{k}: {it[0]}",) + tuple(it[1:]) for k, it in enumerate(items)]   # unique texts
+    assert max(it[2] for it in items) == 17
+    _check_place(asmgen, items, 32)
+
+
+@pytest.mark.parametrize("d", [64, 128, 256])
+def test_tile_swizzle(asmgen, d):
+    """attention.hip's LDS tile comment: 16-B chunks XOR-swizzled per row so that both read
+    shapes are conflict-free (bank = byte / 4 mod 64, i.e. a 256-B bank line of 16 chunk
+    slots)."""
+    swz, toff = asmgen.swz, asmgen.toff_bytes
+    chunks = d // 8
+    slot = lambda r, c8: toff(d, r, 8 * c8) // 16 % 16
+    for r in range(64):
+        # a row's chunks are a permutation of its own chunk slots, elements stay in order
+        assert sorted(toff(d, r, 8 * c) for c in range(chunks)) == \
+            [2 * r * d + 16 * c for c in range(chunks)]
+        assert 0 <= swz(d, r) < min(chunks, 16)
+        for c in range(0, d, 8):
+            assert [toff(d, r, c + e) - toff(d, r, c) for e in range(8)] == list(range(0, 16, 2))
+    for c8 in range(chunks):
+        # 8 consecutive rows: one chunk column falls into 8 distinct slots
+        for r0 in range(64 - 7):
+            assert len({slot(r, c8) for r in range(r0, r0 + 8)}) == 8, (d, c8, r0)
+        # ds_read_b128 row fragments: a 16-lane group reads one chunk of 16 rows
+        # {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} (+32): distinct slots
+        for base in (0, 32):
+            for rows in ((*range(0, 4), *range(12, 16), *range(20, 28)),
+                         (*range(4, 12), *range(16, 20), *range(28, 32))):
+                assert len({slot(base + r, c8) for r in rows}) == 16, (d, c8, base, rows)
+    # ds_read_b64_tr_b16: a 32-lane group reads 4 consecutive chunks of rows 4m..4m+3: the
+    # four 64-B pieces fall in different quarters of the bank line
+    for m in range(16):
+        for c0 in range(0, chunks, 4):
+            quarters = []
+            for r in range(4 * m, 4 * m + 4):
+                q = {slot(r, c0 + k) // 4 for k in range(4)}
+                assert len(q) == 1
+                quarters += q
+            assert sorted(quarters) == [0, 1, 2, 3], (d, m, c0)
+
+
+def test_mad64_and_rsrc_text(asmgen):
+    st = asmgen.Stream()
+    asmgen.mad64(st, "s50", "s51", "s4", "s34", "s35", "s90")
+    assert st.lines == ["\ts_mul_i32 s50, s4, s34",
+                        "\ts_mul_hi_u32 s51, s4, s34",
+                        "\ts_mul_i32 s90, s4, s35",
+                        "\ts_add_u32 s51, s51, s90"]
+    st = asmgen.Stream()
+    asmgen.rsrc(st, "s[56:59]", "s16", "s17", "s44", ("s50", "s51"))
+    assert st.lines == ["\ts_add_u32 s56, s16, s50",
+                        "\ts_addc_u32 s57, s17, s51",
+                        "\ts_and_b32 s57, s57, 0xffff",
+                        "\ts_mov_b32 s58, s44",
+                        "\ts_mov_b32 s59, 0x20000"]
+
+
+def test_generation_ignores_environment(tmp_path):
+    """No switch of the generators is reachable from the environment: the driver writes the
+    same bytes with leftover experiment variables set."""
+    clean = {k: v for k, v in os.environ.items()
+             if not k.startswith("VDIFF_") and k != "PHASE_FLIP"}
+    dirty = dict(clean, VDIFF_ASM_KNOB="gen_fwd.MSUM=2", VDIFF_PHASE_FLIP="all", PHASE_FLIP="all")
+    runs = []
+    for k, env in enumerate((clean, dirty)):   # the two runs side by side
+        out = tmp_path / f"attn_{k}.s"
+        runs.append((out, subprocess.Popen(
+            [sys.executable, os.path.join(ASM, "gen_attn_asm.py"), str(out)], env=env)))
+    outs = []
+    for out, proc in runs:
+        assert proc.wait() == 0
+        outs.append(out.read_bytes())
+    assert len(outs[0]) > 1 << 20 and outs[0] == outs[1]

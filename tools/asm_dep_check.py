@@ -6,8 +6,8 @@ the knob off and on, walks each straight-line text in program order and compares
 A VALU rewrite (packed adds / multiplies, reordering inside a slot) that keeps both equal
 reads the same generation of every value the old schedule read.
 
-    python tools/asm_dep_check.py fwd LAG1       # gen_fwd knob LAG1 0 vs 1: same dependences
-    python tools/asm_dep_check.py fwd GSGS       # a different MFMA order: reports differences
+    python tools/asm_dep_check.py fwd CHECK_NOP  # gen_fwd CHECK_NOP 0 vs 1: same dependences
+    python tools/asm_dep_check.py fwd MSUM       # row sums on the matrix pipe: reports differences
 (kernels: fwd, dq, dkdv, fwd128, dq128, dkdv128).  Used in round 5 for the packed-f32 softmax
 variants (v_pk_add_f32 row sums, v_pk_mul_f32 P * dP; rejected).
 """
