@@ -314,6 +314,28 @@ typedef struct {
 int vd_conv_pack_weights(const vd_pack_desc* descs, int n, int64_t total, int dtype,
                          void* stream);
 
+/* ---- weight EMA (utils.py:92-102 update_ema, for every tensor and rate in ONE launch) ----
+ * For each descriptor, each element i < n and each rate j < k:
+ *   dst[j][i] <- dst[j][i] + (1 - d_j) * (src[i] - dst[j][i])          (fp32, src read once)
+ * d_j = rates[j], or with `warmup` min(rates[j], (float)(1 + c) / (float)(10 + c)) where
+ * c = *num_updates, the updates done before this one (read, never written: the caller
+ * increments it).  If skip_if_nonneg is given and *skip_if_nonneg >= 0 nothing is written
+ * (Trainer's first-bad-step record).  Both words are read on the device when the kernel runs,
+ * so a captured launch replays with their current values.
+ * `descs` is a DEVICE array of n_desc descriptors, one per range of a tensor; the caller cuts
+ * large tensors into ranges of a fixed size, any number of them (blocks walk the table
+ * grid-stride).  A range whose src and k dst pointers are all 16-B aligned moves 8 elements
+ * per lane, any other one element at a time.  dst[j] for j >= k is not read.  One kernel, no
+ * atomics, no memset, no workspace; the result does not depend on the grid.
+ * rates: HOST array of k values in [0, 1). */
+typedef struct {            /* 48 bytes */
+  const float* src;         /* fp32 parameter range                      */
+  float* dst[4];            /* its EMA range per rate; unused slots NULL */
+  int64_t n;                /* elements in the range                     */
+} vd_ema_desc;
+int vd_ema_update(const vd_ema_desc* descs, int n_desc, int k, const float* rates, int warmup,
+                  const int64_t* num_updates, const int64_t* skip_if_nonneg, void* stream);
+
 /* ---- Flash attention --------------------------------------------------
  * replaces QKVAttentionLegacy.forward (unet.py:349-366) + the fp32 softmax
  * (unet.py:364) and, with heads split by strides, QKVAttention (unet.py:

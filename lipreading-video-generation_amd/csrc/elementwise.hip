@@ -797,7 +797,95 @@ __global__ void __launch_bounds__(kBlock) pack_weights_kernel(
   }
 }
 
+// ------------------------------------------------------------ weight EMA
+// One launch for every tracked parameter and up to four rates.  The host cuts each tensor
+// into fixed-size ranges (one vd_ema_desc each); blocks walk that table grid-stride, so the
+// table may be of any length (no in-kernel scan over it as in pack_weights_kernel) and every
+// element belongs to exactly one (descriptor, lane) whatever the grid.  The update count and
+// the bad-step flag are read from device memory, so a captured launch replays with the current
+// count; nothing but the shadows is written.
+namespace {
+
+struct EmaArgs {
+  float rate[4];
+  const int64_t* num_updates;  // read when warmup
+  const int64_t* skip;         // may be null
+  int warmup;
+};
+
+template <int K>
+__global__ void __launch_bounds__(kBlock) ema_kernel(const vd_ema_desc* __restrict__ descs,
+                                                     int n_desc, EmaArgs a) {
+  if (a.skip && *a.skip >= 0) return;
+  float w[K];  // 1 - d_j
+  {
+    float cap = 1.f;
+    if (a.warmup) {
+      const int64_t n = *a.num_updates;
+      cap = (float)(1 + n) / (float)(10 + n);
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) w[j] = 1.0f - (a.warmup ? fminf(a.rate[j], cap) : a.rate[j]);
+  }
+  for (int i = blockIdx.x; i < n_desc; i += gridDim.x) {
+    const vd_ema_desc d = descs[i];
+    uintptr_t align = reinterpret_cast<uintptr_t>(d.src);
+#pragma unroll
+    for (int j = 0; j < K; ++j) align |= reinterpret_cast<uintptr_t>(d.dst[j]);
+    // 8 elements per lane where every pointer allows 16-B accesses, else element by element
+    const int64_t nv = (align % 16 == 0) ? d.n / 8 : 0;
+    for (int64_t v = threadIdx.x; v < nv; v += kBlock) {
+      float p[8], e[K][8];
+      load8(d.src + v * 8, p);  // read once for all K rates; every load before any store
+#pragma unroll
+      for (int j = 0; j < K; ++j) load8(d.dst[j] + v * 8, e[j]);
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) e[j][q] = fmaf(w[j], p[q] - e[j][q], e[j][q]);
+        store8(d.dst[j] + v * 8, e[j]);
+      }
+    }
+    for (int64_t s = nv * 8 + threadIdx.x; s < d.n; s += kBlock) {
+      const float p = d.src[s];
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        const float e = d.dst[j][s];
+        d.dst[j][s] = fmaf(w[j], p - e, e);
+      }
+    }
+  }
+}
+
+}  // namespace
+
 extern "C" {
+
+int vd_ema_update(const vd_ema_desc* descs, int n_desc, int k, const float* rates, int warmup,
+                  const int64_t* num_updates, const int64_t* skip_if_nonneg, void* stream) {
+  VD_REQUIRE(descs && rates, "null argument");
+  VD_REQUIRE(n_desc > 0, "empty descriptor table (n_desc=%d)", n_desc);
+  VD_REQUIRE(k >= 1 && k <= 4, "k=%d outside 1..4", k);
+  EmaArgs a = {};
+  for (int j = 0; j < k; ++j) {
+    VD_REQUIRE(rates[j] >= 0.f && rates[j] < 1.f, "rate %d = %g outside [0, 1)", j,
+               (double)rates[j]);
+    a.rate[j] = rates[j];
+  }
+  VD_REQUIRE(!warmup || num_updates, "warmup needs num_updates");
+  a.num_updates = num_updates;
+  a.skip = skip_if_nonneg;
+  a.warmup = warmup != 0;
+  const int grid = n_desc < 2048 ? n_desc : 2048;  // 8 blocks per CU, then grid-stride
+  hipStream_t st = VD_STREAM(stream);
+  switch (k) {
+    case 1: ema_kernel<1><<<grid, kBlock, 0, st>>>(descs, n_desc, a); break;
+    case 2: ema_kernel<2><<<grid, kBlock, 0, st>>>(descs, n_desc, a); break;
+    case 3: ema_kernel<3><<<grid, kBlock, 0, st>>>(descs, n_desc, a); break;
+    default: ema_kernel<4><<<grid, kBlock, 0, st>>>(descs, n_desc, a); break;
+  }
+  return vd::check_launch("vd_ema_update");
+}
 
 size_t vd_mse_loss_workspace_size(int64_t n) {
   return (size_t)mse_blocks(n) * sizeof(float);

@@ -45,6 +45,11 @@ class XAttnDesc(C.Structure):
                 ("kv_group_stride", _i64), ("kv_token_stride", _i64)]
 
 
+class EmaDesc(C.Structure):
+    """vd_ema_desc: one range of a parameter and of its shadow per rate."""
+    _fields_ = [("src", _vp), ("dst", _vp * 4), ("n", _i64)]
+
+
 _SIGS = {
     "vd_version": (_i, []),
     "vd_last_error": (C.c_char_p, []),
@@ -83,6 +88,7 @@ _SIGS = {
     "vd_channel_sums": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "vd_conv_pack_weight": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vd_conv_pack_weights": (_i, [_vp, _i, _i64, _i, _vp]),
+    "vd_ema_update": (_i, [_vp, _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp]),
     "vd_conv_set_wgrad": (_i, [C.c_int]),
     "vd_conv_set_halo": (_i, [_i]),
     "vd_conv3d_fwd": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -81,7 +81,7 @@ class Trainer:
 
     def __init__(self, model, scheduler, lr=1e-2, bucket_mb=25.0, fused_adam=True,
                  check_every=50, batch_pack=True, graph=False, loss_fn=None,
-                 audio_drop_prob=0.0, drop_generator=None):
+                 audio_drop_prob=0.0, drop_generator=None, ema_rates=(), ema_warmup=False):
         """check_every: the loss finiteness flag (kept on the device, updated every step) is
         read on the host every `check_every` steps and by check_finite(); a non-finite
         loss raises FloatingPointError naming the first bad step.  0 disables it.
@@ -94,7 +94,15 @@ class Trainer:
         audio_drop_prob: share of the clips that train on the null audio (zero features), the
         unconditional half of classifier-free guidance; the model must take `audio_keep`
         (UNetAudio).  0: no mask is drawn and the model is called as before.
-        drop_generator: torch.Generator (on the clips' device) of the keep masks."""
+        drop_generator: torch.Generator (on the clips' device) of the keep masks.
+        ema_rates: decay rates (at most 4) of the weight averages kept in self.ema (vdiff.ema.EMA,
+        None for the empty default); all of them are updated by one launch after each optimizer
+        step, on every path (eager, graph=True, DDP -- each rank keeps its own, identical, copy).
+        The launch reads the first-bad-step record on the device and changes nothing from the
+        first non-finite loss on, so the averages stay clean until check_finite() raises; with
+        check_every=0 there is no record and no such guard.  Under DDP the record is this
+        rank's own loss.
+        ema_warmup: decay min(rate, (1 + n) / (10 + n)) after n updates."""
         if not 0.0 <= audio_drop_prob <= 1.0:
             raise ValueError(f"audio_drop_prob {audio_drop_prob} outside [0, 1]")
         self.audio_drop_prob = float(audio_drop_prob)
@@ -126,6 +134,10 @@ class Trainer:
                                "step (kernel-bound; DESIGN section 9 item 3); set "
                                "VDIFF_TRAIN_GRAPH_EXPERIMENTAL=1 to run it")
         self.graph = TrainStepGraph(self) if graph else None
+        self.ema = None
+        if len(tuple(ema_rates)):
+            from .ema import EMA
+            self.ema = EMA(model, ema_rates, warmup=ema_warmup)
 
     def step(self, clip: Clip) -> torch.Tensor:
         if self.graph is not None:
@@ -159,7 +171,13 @@ class Trainer:
             self.opt.zero_grad(set_to_none=True)
         loss = loss.detach()
         self._track_finite(loss)
+        self._update_ema()
         return loss
+
+    def _update_ema(self):
+        """After the optimizer step and this step's entry in the first-bad-step record."""
+        if self.ema is not None:
+            self.ema.update(skip_flag=self._first_bad)
 
     def _track_finite(self, loss):
         """SURVEY 5 failure detection without a per-step host sync: a device-side record of
@@ -270,6 +288,7 @@ class TrainStepGraph:
         self.steps += 1
         loss = self.loss.clone()  # the replay's own MSE (vd_mse_loss, captured)
         tr._track_finite(loss)
+        tr._update_ema()  # eager, like Adam: one launch and the count's increment
         return loss
 
     def node_types(self):

@@ -724,6 +724,22 @@ def _pack_weight_now(weight, Co, Ci, taps, Cip, Cop, transpose, dt):
     return out
 
 
+def ema_update(table, n_desc, rates, warmup=False, num_updates=None, skip_flag=None):
+    """One vd_ema_update launch on the current stream: every range of the device descriptor
+    table `table` (uint8 image of n_desc vd_ema_desc, vdiff.ema builds it), every rate of
+    `rates` (host floats in [0, 1), at most 4).  num_updates / skip_flag: int64 device scalars,
+    read by the kernel (the update count of the warm-up decay; >= 0 skips the launch's writes).
+    No host sync."""
+    _gpu(table, num_updates, skip_flag)
+    for t in (num_updates, skip_flag):
+        if t is not None and t.dtype != torch.int64:
+            raise TypeError(f"ema_update: int64 device scalars, got {t.dtype}")
+    k = len(rates)
+    arr = (_lib.C.c_float * max(k, 1))(*[float(r) for r in rates])
+    _lib.call("vd_ema_update", _p(table), int(n_desc), k, arr, int(bool(warmup)),
+              _p(num_updates), _p(skip_flag), _stream(table))
+
+
 def channel_sums(x: torch.Tensor) -> torch.Tensor:
     """[B, C, *spatial] channels-last -> fp32 [B, C] sums over the spatial dims."""
     _gpu(x)

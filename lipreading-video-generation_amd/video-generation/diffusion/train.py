@@ -15,12 +15,14 @@ Initialisation is the reference's (zero_module layers included, unet.py:222-224,
 627) and wav2vec2 must load its pretrained weights (unet_audio.py:14) unless
 --random-audio-encoder (or --resume, whose checkpoint carries them) is given;
 --reinit-nonzero replaces the zero-initialised layers with seeded weights (benchmarks and
-smoke runs only).
+smoke runs only).  --ema-rate R [R ...] keeps exponential moving averages of the weights
+(vdiff.ema) and saves them as <ckpt>.ema_<R>, state dicts that test.py --ckpt loads.
 """
 import argparse
 import os
 import sys
 import time
+import warnings
 
 import torch
 
@@ -69,6 +71,12 @@ def parse(argv=None):
     ap.add_argument("--audio-drop-prob", type=float, default=0.0,
                     help="share of the clips trained on the null audio (0.1-0.2 for a model "
                          "sampled with test.py --guidance-scale; build extension)")
+    ap.add_argument("--ema-rate", type=float, nargs="+", default=[], metavar="R",
+                    help="keep an exponential moving average of the weights per rate (at most "
+                         "4, e.g. 0.9999); saved as <ckpt>.ema_<rate>, a state dict for test.py "
+                         "--ckpt (build extension; default: none)")
+    ap.add_argument("--ema-warmup", action="store_true",
+                    help="EMA decay min(rate, (1 + n) / (10 + n)) after n updates")
     ap.add_argument("--reinit-nonzero", action="store_true",
                     help="seeded weights for the zero-initialised layers (smoke / bench only)")
     return ap.parse_args(argv)
@@ -109,13 +117,21 @@ def train(argv=None):
     if args.audio_drop_prob > 0:  # the keep masks: a seeded stream of their own per rank
         drop_gen = torch.Generator(device=device).manual_seed(args.seed * 7919 + rank)
     trainer = Trainer(model, scheduler, lr=args.lr, audio_drop_prob=args.audio_drop_prob,
-                      drop_generator=drop_gen)
+                      drop_generator=drop_gen, ema_rates=tuple(args.ema_rate),
+                      ema_warmup=args.ema_warmup)
     start_epoch = 0
     if args.resume:
         state = torch.load(args.resume, map_location=device, weights_only=True)
         model.load_state_dict(state["model"])
         trainer.opt.load_state_dict(state["optimizer"])
         start_epoch = int(state["epoch"]) + 1
+        if trainer.ema is not None:
+            if "ema" in state:
+                trainer.ema.load_checkpoint(state["ema"])
+            else:
+                warnings.warn(f"{args.resume} holds no EMA: the averages start from the "
+                              "loaded weights")
+                trainer.ema.reset_to_parameters()
     if rank == 0:
         print(f"Training on {device} x{world}: {sum(p.numel() for p in model.parameters()) / 1e6:.1f}"
               f" M params, dims={args.dims}, {args.attention_mode} attention, {args.dtype}")
@@ -149,8 +165,14 @@ def train(argv=None):
             print(f"Finished epoch {epoch + 1} | Loss: {loss.item()} | mean "
                   f"{loss_sum.item() / args.steps_per_epoch:.5f} | {fps:.2f} frames/s", flush=True)
             torch.save(model.state_dict(), args.ckpt)
-            torch.save({"model": model.state_dict(), "optimizer": trainer.opt.state_dict(),
-                        "epoch": epoch}, args.ckpt + ".resume")
+            resume = {"model": model.state_dict(), "optimizer": trainer.opt.state_dict(),
+                      "epoch": epoch}
+            if trainer.ema is not None:
+                resume["ema"] = trainer.ema.checkpoint()
+                for rate in trainer.ema.rates:
+                    torch.save(trainer.ema.state_dict(rate), f"{args.ckpt}.ema_{rate}")
+                print(f"EMA updates: {int(trainer.ema.num_updates)}", flush=True)
+            torch.save(resume, args.ckpt + ".resume")
     if rank == 0:
         print("Done Training ...")
     return float(loss)
