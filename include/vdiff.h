@@ -152,6 +152,29 @@ int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w,
                    const void* workspace, int64_t B, int64_t per_sample, int dtype,
                    void* stream);
 
+/* DPM-Solver++(2M) step (Lu et al. 2022; build extension, no reference counterpart): a
+ * second-order multistep update that reuses the previous step's x0 instead of a second forward.
+ * coef: fp32 [n_steps][8], row i = [alpha_t, sigma_t, A, B, C, 0, 0, 0], computed in fp64 on
+ * the host (vdiff.schedulers.DPMSolverSampler) and rounded once.
+ *   x0 = (xt - sigma_t eps) / alpha_t [clamped to [-1,1] if clip];
+ *   x_prev = A xt + B x0 + C x0_last, from the fp32 x0.
+ * step: a DEVICE int64 scalar, the row index, clamped into [0, n_steps - 1] by the kernel: the
+ * launch arguments are the same at every step, so one captured graph replays for all of them.
+ * x0_hist holds x0_last on entry and x0 on return (in place; never NULL).  A row whose C is
+ * exactly 0 (the first-order rows and the last one) does NOT read x0_hist, which may then be
+ * uninitialised.  x_prev may alias xt.
+ * vd_dpm_step_cfg: guide, rescale and the same update in one pass, as vd_ddim_step_cfg: eps =
+ * f_b (eps_u + w (eps_c - eps_u)); x_prev_dup (may be NULL) receives x_prev's values too;
+ * rescale > 0 reads the vd_cfg_stats workspace, rescale == 0 accepts a NULL one.
+ * Plain vector loads and stores: no atomics, no memset, no LDS beyond the f_b sum. */
+int vd_dpm_step(const void* xt, const void* eps, void* x_prev, void* x0_hist,
+                const float* coef, int64_t n_steps, const int64_t* step, int clip,
+                int64_t B, int64_t per_sample, int dtype, void* stream);
+int vd_dpm_step_cfg(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
+                    void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
+                    const int64_t* step, float w, float rescale, const void* workspace,
+                    int clip, int64_t B, int64_t per_sample, int dtype, void* stream);
+
 /* ---- GroupNorm (+SiLU) -------------------------------------------------
  * replaces GroupNorm32 (utils.py:54-56, fp32 statistics) followed by nn.SiLU
  * (unet.py:194-198, 218-225, 297, 624-628).  x, y: [B][S][C] channels-last,

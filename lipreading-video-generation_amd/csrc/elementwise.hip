@@ -526,6 +526,93 @@ inline bool cfg_vec8(int64_t per_sample, std::initializer_list<const void*> ptrs
   return per_sample % 8 == 0 && a % 16 == 0;
 }
 
+// ------------------------------------------------------------ DPM-Solver++(2M) step
+// x0 = (xt - sigma_t eps) / alpha_t, x_prev = A xt + B x0 + C x0_last, with the row [alpha_t,
+// sigma_t, A, B, C, 0, 0, 0] of the host's fp32 table picked by a device scalar: the launch
+// arguments never change, so a captured graph replays for every step.  The row is uniform
+// across the launch.  C == 0 (the first-order rows and the last one): the history is not read
+// -- at step 0 it is uninitialised, and 0 * NaN is NaN.
+struct DPMStep {
+  const float* coef;
+  int64_t n_steps;
+  const int64_t* step;
+  int clip;
+  struct Row {
+    float alpha, sigma, A, B, C;
+  };
+  __device__ __forceinline__ Row row() const {
+    int64_t s = *step;
+    s = s < 0 ? 0 : (s > n_steps - 1 ? n_steps - 1 : s);
+    const float* r = coef + s * 8;
+    return Row{r[0], r[1], r[2], r[3], r[4]};
+  }
+  // x_prev is formed from the fp32 x0, not from the value a bf16 history rounds it to
+  __device__ __forceinline__ void run(const Row& r, bool hist, const float* xt, const float* eps,
+                                      const float* last, float* xprev, float* x0o, int n) const {
+    for (int i = 0; i < n; ++i) {
+      float x0 = (xt[i] - r.sigma * eps[i]) / r.alpha;
+      if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+      x0o[i] = x0;
+      float v = r.A * xt[i] + r.B * x0;
+      if (hist) v += r.C * last[i];
+      xprev[i] = v;
+    }
+  }
+};
+
+// Three reads (xt, eps, the history when C != 0), two writes (x_prev, the history in place).
+// xprev may alias xt and `hist` is read and written: a lane reads its elements before it
+// writes them, and no other lane touches them.
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kBlock) dpm_kernel(DPMStep op, const T* xt,
+                                                     const T* __restrict__ eps, T* xprev,
+                                                     T* hist, int64_t n) {
+  const DPMStep::Row r = op.row();
+  const bool use_hist = r.C != 0.f;
+  const int64_t nvec = n / VEC;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = v * VEC;
+    float xa[8], xb[8], xh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, y0[8], y1[8];
+    ld_vec(xt + e, xa, VEC);
+    ld_vec(eps + e, xb, VEC);
+    if (use_hist) ld_vec(hist + e, xh, VEC);
+    op.run(r, use_hist, xa, xb, xh, y0, y1, VEC);
+    st_vec(xprev + e, y0, VEC);
+    st_vec(hist + e, y1, VEC);
+  }
+}
+
+// Guide + rescale + the step above in one pass, laid out as cfg_ddim_kernel: blockIdx.y =
+// sample, one f_b per block, x_prev written twice when xdup is given.
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kBlock) cfg_dpm_kernel(
+    DPMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
+    T* xprev, T* xdup, T* hist, const float* __restrict__ part, int nb, float phi,
+    int64_t per_sample) {
+  const int64_t b = blockIdx.y;
+  const bool scale = phi > 0.f;
+  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
+  const DPMStep::Row r = op.row();
+  const bool use_hist = r.C != 0.f;
+  const int64_t base = b * per_sample;
+  const int64_t nvec = per_sample / VEC;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = base + v * VEC;
+    float xa[8], xc[8], xu[8], xh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
+    ld_vec(xt + e, xa, VEC);
+    ld_vec(c + e, xc, VEC);
+    ld_vec(u + e, xu, VEC);
+    if (use_hist) ld_vec(hist + e, xh, VEC);
+    gd.run(xc, xu, f, scale, g, VEC);
+    op.run(r, use_hist, xa, g, xh, y0, y1, VEC);
+    st_vec(xprev + e, y0, VEC);
+    if (xdup) st_vec(xdup + e, y0, VEC);
+    st_vec(hist + e, y1, VEC);
+  }
+}
+
 inline dim3 cfg_grid(int64_t per_sample, int vec, int64_t B) {
   return dim3((unsigned)grid_for(per_sample / vec), (unsigned)B);
 }
@@ -1067,6 +1154,54 @@ int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const
       cfg_ddim_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
           op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
           (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
+  });
+}
+
+int vd_dpm_step(const void* xt, const void* eps, void* x_prev, void* x0_hist, const float* coef,
+                int64_t n_steps, const int64_t* step, int clip, int64_t B, int64_t per_sample,
+                int dtype, void* stream) {
+  VD_REQUIRE(xt && eps && x_prev && x0_hist && coef && step, "null argument");
+  VD_REQUIRE(B > 0 && per_sample > 0 && n_steps > 0,
+             "empty tensor or table (B=%lld, per_sample=%lld, n_steps=%lld)", (long long)B,
+             (long long)per_sample, (long long)n_steps);
+  DPMStep op{coef, n_steps, step, clip};
+  const bool v8 = cfg_vec8(per_sample, {xt, eps, x_prev, x0_hist});
+  const int64_t n = B * per_sample;
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (v8)
+      dpm_kernel<T, 8><<<grid_for(n / 8), kBlock, 0, VD_STREAM(stream)>>>(
+          op, (const T*)xt, (const T*)eps, (T*)x_prev, (T*)x0_hist, n);
+    else
+      dpm_kernel<T, 1><<<grid_for(n), kBlock, 0, VD_STREAM(stream)>>>(
+          op, (const T*)xt, (const T*)eps, (T*)x_prev, (T*)x0_hist, n);
+  });
+}
+
+int vd_dpm_step_cfg(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
+                    void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
+                    const int64_t* step, float w, float rescale, const void* workspace, int clip,
+                    int64_t B, int64_t per_sample, int dtype, void* stream) {
+  VD_REQUIRE(xt && eps_c && eps_u && x_prev && x0_hist && coef && step, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && n_steps > 0,
+             "bad shape (B=%lld, per_sample=%lld, n_steps=%lld)", (long long)B,
+             (long long)per_sample, (long long)n_steps);
+  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
+  VD_REQUIRE(rescale == 0.f || workspace, "rescale > 0 needs the vd_cfg_stats workspace (null)");
+  DPMStep op{coef, n_steps, step, clip};
+  const CfgGuide gd{w};
+  const int nb = cfg_blocks(per_sample);
+  const float* part = static_cast<const float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist});
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (v8)
+      cfg_dpm_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
+          (T*)x0_hist, part, nb, rescale, per_sample);
+    else
+      cfg_dpm_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
+          (T*)x0_hist, part, nb, rescale, per_sample);
   });
 }
 

@@ -67,6 +67,9 @@ _SIGS = {
     "vd_ddim_step_cfg": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f,
                               _i, _i64, _i64, _i, _vp]),
     "vd_cfg_combine": (_i, [_vp, _vp, _vp, _f, _f, _vp, _i64, _i64, _i, _vp]),
+    "vd_dpm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _vp]),
+    "vd_dpm_step_cfg": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i, _i64,
+                             _i64, _i, _vp]),
     "vd_set_dropout_counter": (None, [_vp]),
     "vd_groupnorm_set_unroll": (_i, [_i]),
     "vd_groupnorm_workspace_size": (_sz, [_i, _i64, _i, _i]),

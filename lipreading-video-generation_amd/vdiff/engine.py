@@ -456,7 +456,7 @@ class DDIMGraph:
             # a memset node replayed with eager work between replays is
             # where a captured reduction went stale on this HIP runtime; sample() steps
             # eagerly instead of trusting such a graph
-            raise GraphUnsafe(f"DDIMGraph: captured step holds memset nodes {types}")
+            raise GraphUnsafe(f"{type(self).__name__}: captured step holds memset nodes {types}")
 
     def node_types(self):
         """{node type: count} of the captured step (vdiff.hipgraph; memset nodes must be 0)."""
@@ -510,6 +510,108 @@ def _sample_ddim(model, sampler, cond, audio, shape, generator, callback, scale=
             xt, x0 = sampler.step(xt, model(xt, cond, feats, t), i)
         if callback is not None:
             callback(i, xt, x0)
+    return xt, x0
+
+
+class DPMGraph(DDIMGraph):
+    """One DPM-Solver++(2M) step -- UNet forward + vd_dpm_step, or at batch 2B + vd_cfg_stats +
+    vd_dpm_step_cfg when guided -- captured once and replayed for every step: the kernel picks
+    its coefficient row by a device scalar, so the first-order, second-order and last steps
+    differ only in the table.  On top of DDIMGraph's static sample the graph owns the x0
+    history (read as the previous step's x0, written in place; x_prev is written over xt) and
+    the step-index scalar, copied device-to-device before each replay like the timesteps."""
+
+    def __init__(self, model, sampler, cond, feats, xt, guidance_scale=1.0, guidance_rescale=0.0):
+        dev = xt.device
+        B = xt.shape[0]
+        self.model, self.sampler = model, sampler
+        self.scale, self.rescale = float(guidance_scale), float(guidance_rescale)
+        self.guided = self.scale != 1.0
+        if self.guided:
+            cond, feats = _doubled(cond, feats)
+            self.x2 = torch.cat([xt, xt])
+            self.xt, self.xdup = self.x2[:B], self.x2[B:]
+            B = 2 * B
+        else:
+            self.xt = xt.clone()
+        self.cond, self.feats = cond, feats
+        self.t_all = sampler.timesteps.to(dev).view(-1, 1).expand(-1, B).contiguous()
+        self.t = self.t_all[0].clone()
+        self.coef, self.idx_all = sampler._tables(dev)
+        self.idx = self.idx_all[:1].clone()
+        # uninitialised on purpose: row 0 has C == 0 and does not read it
+        self.x0 = torch.empty_like(self.xt, memory_format=torch.contiguous_format)
+        self.graph = None
+
+    def _body(self):
+        clip = self.sampler.clip_x0
+        if self.guided:
+            eps = self.model(self.x2, self.cond, self.feats, self.t)
+            eps_c, eps_u = eps.to(self.xt.dtype).chunk(2)
+            ops.dpm_step_cfg(self.xt, eps_c, eps_u, self.x0, self.coef, self.idx, self.scale,
+                             self.rescale, clip=clip, out=self.xt, dup=self.xdup)
+        else:
+            eps = self.model(self.xt, self.cond, self.feats, self.t)
+            ops.dpm_step(self.xt, eps.to(self.xt.dtype), self.x0, self.coef, self.idx,
+                         clip=clip, out=self.xt)
+        return self.x0
+
+    def step(self, i):
+        """Denoise from sampler.timesteps[i]; returns (x_prev, x0) (static buffers).  Steps run
+        in order: step i reads the x0 that step i - 1 left in the history."""
+        self.t.copy_(self.t_all[i])
+        self.idx.copy_(self.idx_all[i:i + 1])
+        if self.graph is None:
+            self.capture()
+        self.graph.replay()
+        return self.xt, self.x0
+
+
+@torch.no_grad()
+def sample_dpm(model, sampler, cond, audio, shape, generator=None, callback=None,
+               guidance_scale=1.0, guidance_rescale=0.0):
+    """DPM-Solver++(2M) sampling (schedulers.DPMSolverSampler) with sample_ddim's contract:
+    audio encoded once, packed conv weights reused across the steps, callback(i, xt, x0) at
+    every step, classifier-free audio guidance as one forward at batch 2B, and on a GPU one
+    replayed graph (DPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which launches the same
+    kernels on the same operands)."""
+    with ops.frozen_weights():
+        return _sample_dpm(model, sampler, cond, audio, shape, generator, callback,
+                           float(guidance_scale), float(guidance_rescale))
+
+
+def _sample_dpm(model, sampler, cond, audio, shape, generator, callback, scale=1.0, rescale=0.0):
+    model.eval()
+    device = cond.device
+    feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
+    xt = torch.randn(shape, generator=generator, device=device)
+    x0 = None
+    if device.type == "cuda" and os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0":
+        g = DPMGraph(model, sampler, cond, feats, xt, scale, rescale)
+        try:
+            g.capture()
+        except GraphUnsafe as e:
+            warnings.warn(f"{e}; sampling eagerly")
+            g = None
+        if g is not None:
+            for i in range(sampler.steps):
+                xt, x0 = g.step(i)
+                if callback is not None:  # the graph's static buffers: the next replay rewrites them
+                    callback(i, xt.clone(), x0.clone())
+            return xt.clone(), x0.clone()
+    guided = scale != 1.0
+    if guided:
+        cond, feats = _doubled(cond, feats)
+    nb = (2 if guided else 1) * shape[0]
+    for i in range(sampler.steps):
+        t = torch.full((nb,), int(sampler.timesteps[i]), dtype=torch.int64, device=device)
+        if guided:
+            eps_c, eps_u = model(torch.cat([xt, xt]), cond, feats, t).chunk(2)
+            xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale, x0_last=x0)
+        else:
+            xt, x0 = sampler.step(xt, model(xt, cond, feats, t), i, x0_last=x0)
+        if callback is not None:  # x0 is the history buffer: the next step rewrites it
+            callback(i, xt, x0.clone())
     return xt, x0
 
 

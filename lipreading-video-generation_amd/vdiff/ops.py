@@ -248,6 +248,57 @@ def ddim_step_cfg(xt, eps_c, eps_u, t, t_prev, acp, scale, rescale=0.0, eta=0.0,
     return xp, x0
 
 
+def _dpm_args(xt, x0_hist, coef, step, out, dup=None):
+    """Checked (x_prev buffer, n_steps) of a DPM-Solver++ step: x0_hist / out / dup contiguous
+    buffers like xt, coef the fp32 [n_steps, 8] device table, step a device int64 scalar."""
+    if x0_hist is None:
+        raise ValueError("dpm_step: x0_hist is the kernel's x0 output too and may not be None")
+    _gpu(x0_hist, coef, step, out, dup)
+    xp =torch.empty_like(xt) if out is None else out
+    for name, buf in (("x0_hist", x0_hist), ("out", xp), ("dup", dup)):
+        if buf is not None and (buf.dtype != xt.dtype or buf.numel() != xt.numel()
+                                or not buf.is_contiguous()):
+            raise ValueError(f"dpm_step: `{name}` must be a contiguous buffer like xt")
+    if coef.dtype != torch.float32 or coef.dim() != 2 or coef.shape[1] != 8 \
+            or coef.shape[0] < 1 or not coef.is_contiguous():
+        raise ValueError("dpm_step: coef must be a contiguous fp32 [n_steps, 8] table")
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise ValueError("dpm_step: step must be an int64 tensor with one element")
+    return xp, coef.shape[0]
+
+
+def dpm_step(xt, eps, x0_hist, coef, step, clip=False, out=None):
+    """One DPM-Solver++(2M) update (vd_dpm_step) from row `step` of the sampler's coefficient
+    table: (x_prev, x0).  x0_hist holds the previous step's x0 and is overwritten in place with
+    this step's (the returned x0 is that buffer); a row with C == 0 does not read it.  step: a
+    device int64 scalar.  out: x_prev's buffer (may be xt itself)."""
+    _gpu(xt, eps)
+    xt, eps = _flat(xt), _flat(eps)
+    if eps.dtype != xt.dtype or eps.shape != xt.shape:
+        raise ValueError("xt / eps mismatch")
+    xp, n_steps = _dpm_args(xt, x0_hist, coef, step, out)
+    B = xt.shape[0]
+    _lib.call("vd_dpm_step", _p(xt), _p(eps), _p(xp), _p(x0_hist), _p(coef), n_steps, _p(step),
+              int(bool(clip)), B, xt.numel() // B, _dtype(xt), _stream(xt))
+    return xp, x0_hist
+
+
+def dpm_step_cfg(xt, eps_c, eps_u, x0_hist, coef, step, scale, rescale=0.0, clip=False,
+                 out=None, dup=None):
+    """dpm_step on the guided noise of cfg_combine, in one pass (vd_dpm_step_cfg): (x_prev, x0).
+    out / dup as in ddim_step_cfg."""
+    _gpu(xt)
+    xt = _flat(xt)
+    eps_c, eps_u, B, P, ws = _cfg_args(eps_c, eps_u, scale, rescale)
+    if eps_c.dtype != xt.dtype or eps_c.shape != xt.shape:
+        raise ValueError("xt / eps mismatch")
+    xp, n_steps = _dpm_args(xt, x0_hist, coef, step, out, dup)
+    _lib.call("vd_dpm_step_cfg", _p(xt), _p(eps_c), _p(eps_u), _p(xp), _p(dup), _p(x0_hist),
+              _p(coef), n_steps, _p(step), float(scale), float(rescale), _p(ws),
+              int(bool(clip)), B, P, _dtype(xt), _stream(xt))
+    return xp, x0_hist
+
+
 # --------------------------------------------------------------- GroupNorm+SiLU
 class GroupNormSiLUFn(torch.autograd.Function):
     """y = dropout(silu(GN(x))).  With `passthrough`, forward also returns x itself (an alias)

@@ -1,5 +1,5 @@
 """DDPM schedulers with the reference API (linear_noise_scheduler.py, noise_scheduler.py)
-plus a DDIM sampler, all running on the HIP scheduler kernels.
+plus a DDIM and a DPM-Solver++(2M) sampler, all running on the HIP scheduler kernels.
 
 The schedule tables are built on the host exactly as the reference builds them (same
 torch CPU ops, so they are bit-identical and keep the reference attribute names);
@@ -147,3 +147,122 @@ class DDIMSampler:
         return ops.ddim_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
                                  eps_u.contiguous().to(xt.dtype), t, tp, self._acp(xt.device),
                                  scale, rescale, eta=self.eta, z=z, clip=self.clip_x0)
+
+
+class DPMSolverSampler:
+    """DPM-Solver++(2M) (Lu et al. 2022): a deterministic second-order multistep sampler over a
+    subsequence of a DDPM schedule's acp table.  It reuses the previous step's x0 prediction
+    instead of a second forward, so a step costs what a DDIM step costs.  This is diffusers'
+    DPMSolverMultistepScheduler with algorithm_type="dpmsolver++", solver_type="midpoint",
+    lower_order_final=True and a zero final sigma; noise (epsilon) prediction only.  Not here:
+    the stochastic (SDE) variants, third-order and singlestep solvers, dynamic thresholding and
+    v-prediction.
+
+    With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h = lambda_prev -
+    lambda_t and k = -alpha_prev expm1(-h), a step is
+
+        x0 = (xt - sigma_t eps) / alpha_t          (clamped to [-1, 1] if clip_x0)
+        x_prev = A xt + B x0 + C x0_last
+
+    first order (row 0, and every row with order=1): A = sigma_prev / sigma_t, B = k, C = 0 --
+    the DDIM update; second order, r = (lambda_t - lambda_last) / h: B = k (1 + 1 / (2 r)), C =
+    -k / (2 r); last row (t_prev = -1: a = 1, sigma = 0): A = 0, B = 1, C = 0, x_prev = x0.
+    self.coef64 holds the rows [alpha_t, sigma_t, A, B, C, 0, 0, 0] in fp64, self.coef the same
+    rounded once to fp32: the table the kernel reads.
+
+    spacing: "logsnr" (default) picks the timesteps nearest to `steps` values of lambda spread
+    uniformly from lambda[T-1] to lambda[0] (lowest index on a tie, duplicates dropped, so
+    self.steps may be smaller than asked for); "linspace" is DDIMSampler's rule.  On linspace
+    timesteps the last steps span a huge lambda interval and the second order buys nothing below
+    about 20 steps.
+
+    The sampler keeps no history: step() takes the previous step's x0 and returns this one's.
+    """
+
+    def __init__(self, scheduler, steps=20, order=2, spacing="logsnr", clip_x0=False):
+        acp = getattr(scheduler, "alpha_cum_prod", None)
+        if acp is None:
+            acp = scheduler.alphas_cumprod
+        if steps < 1:
+            raise ValueError(f"DPMSolverSampler: steps {steps} < 1")
+        if order not in (1, 2):
+            raise ValueError(f"DPMSolverSampler: order {order} not in (1, 2)")
+        self.acp = acp.float()
+        self.num_train_timesteps = T = acp.numel()
+        self.order = order
+        self.spacing = spacing
+        self.clip_x0 = clip_x0
+        a = self.acp.double()
+        if spacing == "linspace":
+            ts = torch.linspace(T - 1, 0, steps).round().long()
+        elif spacing == "logsnr":
+            if not bool(((a > 0) & (a < 1)).all()):
+                raise ValueError("DPMSolverSampler: cumulative alphas outside (0, 1)")
+            lam = 0.5 * torch.log(a / (1 - a))
+            targets = torch.linspace(float(lam[T - 1]), float(lam[0]), steps, dtype=torch.float64)
+            # argmin returns the lowest index among equal distances
+            idx = (lam.view(1, -1) - targets.view(-1, 1)).abs().argmin(dim=1)
+            ts = torch.unique(idx).flip(0)  # unique sorts ascending
+        else:
+            raise ValueError(f"DPMSolverSampler: unknown spacing {spacing!r}")
+        at = a[ts]
+        if not bool(((at > 0) & (at < 1)).all()):
+            raise ValueError("DPMSolverSampler: a selected cumulative alpha is outside (0, 1)")
+        self.timesteps = ts
+        self.prev_timesteps = torch.cat([ts[1:], torch.tensor([-1])])
+        self.steps = n = ts.numel()
+        alpha, sigma = at.sqrt(), (1 - at).sqrt()
+        lam = torch.log(alpha / sigma)
+        coef = torch.zeros((n, 8), dtype=torch.float64)
+        coef[:, 0], coef[:, 1] = alpha, sigma
+        for i in range(n - 1):
+            h = lam[i + 1] - lam[i]
+            k = -alpha[i + 1] * torch.expm1(-h)
+            coef[i, 2] = sigma[i + 1] / sigma[i]
+            if order == 2 and i > 0:
+                r = (lam[i] - lam[i - 1]) / h
+                coef[i, 3], coef[i, 4] = k * (1 + 1 / (2 * r)), -k / (2 * r)
+            else:
+                coef[i, 3] = k
+        coef[n - 1, 3] = 1.0
+        self.coef64 = coef
+        self.coef = coef.float()
+        self._dev = {}
+
+    def _tables(self, device):
+        """(coef, arange(steps)) on the device: the kernel takes its row index from there."""
+        k = str(device)
+        if k not in self._dev:
+            self._dev[k] = (self.coef.to(device).contiguous(),
+                            torch.arange(self.steps, dtype=torch.int64, device=device))
+        return self._dev[k]
+
+    def _hist(self, xt, i, x0_last):
+        if not 0 <= i < self.steps:
+            raise IndexError(f"DPMSolverSampler: step {i} outside [0, {self.steps})")
+        if x0_last is not None:
+            return x0_last
+        if float(self.coef[i, 4]) != 0.0:
+            raise ValueError(f"DPMSolverSampler: step {i} is a second-order row and needs "
+                             "x0_last, the x0 that step i - 1 returned")
+        return torch.empty_like(xt, memory_format=torch.contiguous_format)
+
+    def step(self, xt, noise_pred, i, x0_last=None):
+        """One update from self.timesteps[i] to self.prev_timesteps[i]: (x_prev, x0).  x0_last:
+        the x0 that step i - 1 returned; it is overwritten in place with this step's x0 and
+        returned.  None is allowed where the row does not read it (C == 0)."""
+        i = int(i)
+        hist = self._hist(xt, i, x0_last)
+        coef, idx = self._tables(xt.device)
+        return ops.dpm_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), hist, coef,
+                            idx[i:i + 1], clip=self.clip_x0)
+
+    def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, x0_last=None):
+        """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
+        by `rescale`: guide, rescale and update in one kernel (ops.dpm_step_cfg)."""
+        i = int(i)
+        hist = self._hist(xt, i, x0_last)
+        coef, idx = self._tables(xt.device)
+        return ops.dpm_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
+                                eps_u.contiguous().to(xt.dtype), hist, coef, idx[i:i + 1], scale,
+                                rescale, clip=self.clip_x0)

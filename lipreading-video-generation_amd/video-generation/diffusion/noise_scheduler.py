@@ -1,4 +1,4 @@
 """Drop-in for video-generation/diffusion/noise_scheduler.py (HIP kernels), plus the
-build's DDIM sampler."""
+build's DDIM and DPM-Solver++(2M) samplers."""
 import _vdiff_path  # noqa: F401
-from vdiff.schedulers import CosineNoiseScheduler, DDIMSampler  # noqa: F401
+from vdiff.schedulers import CosineNoiseScheduler, DDIMSampler, DPMSolverSampler  # noqa: F401

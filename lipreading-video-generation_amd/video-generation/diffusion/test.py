@@ -1,6 +1,7 @@
 """Sampling entry point (drop-in for video-generation/diffusion/test.py) on MI355X.
 
-    python test.py [--ckpt model.pth | --random-init] [--sampler ddpm-v2|ddim] [--steps 500]
+    python test.py [--ckpt model.pth | --random-init] [--sampler ddpm-v2|ddim|dpm++]
+                   [--steps 500] [--spacing logsnr|linspace]
                    [--guidance-scale 1.0] [--guidance-rescale 0.0]
 
 Reference API kept (importable without running anything, unlike the reference script):
@@ -31,11 +32,11 @@ import numpy as np
 import torch
 
 import _vdiff_path  # noqa: F401
-from vdiff.engine import reinit_nonzero, sample_ddim, synthetic_clip
+from vdiff.engine import reinit_nonzero, sample_ddim, sample_dpm, synthetic_clip
 from vdiff.ops import cfg_combine, frozen_weights
 
 from linear_noise_scheduler import LinearNoiseSchedulerV2
-from noise_scheduler import DDIMSampler
+from noise_scheduler import DDIMSampler, DPMSolverSampler
 from unet_audio import UNetAudio
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -168,8 +169,12 @@ def parse(argv=None):
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--random-init", action="store_true",
                     help="no checkpoint: seeded smoke weights and a random wav2vec2")
-    ap.add_argument("--sampler", default="ddpm-v2", choices=["ddpm-v2", "ddim"])
-    ap.add_argument("--steps", type=int, default=None, help="500 (ddpm-v2) / 50 (ddim)")
+    ap.add_argument("--sampler", default="ddpm-v2", choices=["ddpm-v2", "ddim", "dpm++"],
+                    help="dpm++: DPM-Solver++(2M), second-order multistep, deterministic")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="500 (ddpm-v2) / 50 (ddim) / 20 (dpm++)")
+    ap.add_argument("--spacing", default="logsnr", choices=["logsnr", "linspace"],
+                    help="dpm++ timesteps: uniform in log-SNR (default) or DDIM's linspace")
     ap.add_argument("--dims", type=int, default=2)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--image-size", type=int, default=config["dataset_params"]["im_size"])
@@ -186,7 +191,10 @@ def parse(argv=None):
                          "with --audio-drop-prob)")
     ap.add_argument("--guidance-rescale", type=float, default=0.0,
                     help="std-rescale of the guided noise in [0, 1] (Lin et al. 2023)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps is None and args.sampler == "dpm++":
+        args.steps = 20
+    return args
 
 
 def main(argv=None):
@@ -216,19 +224,23 @@ def main(argv=None):
                               dims=args.dims)
         cond, audio = clip.cond, clip.audio
     g = torch.Generator(device=device).manual_seed(args.seed)
-    if args.sampler == "ddim":
+    if args.sampler in ("ddim", "dpm++"):
         os.makedirs(args.out_dir, exist_ok=True)
         shape = (1, 3, frames, args.image_size, args.image_size) if args.dims == 3 else \
             (1, 3, args.image_size, args.image_size)
-        sampler = DDIMSampler(scheduler, steps=args.steps or 50)
+        if args.sampler == "ddim":
+            sampler, sample = DDIMSampler(scheduler, steps=args.steps or 50), sample_ddim
+        else:
+            sampler = DPMSolverSampler(scheduler, steps=args.steps or 20, spacing=args.spacing)
+            sample = sample_dpm
 
         def cb(i, xt, x0):
             if (i + 1) % args.save_every == 0 or i == sampler.steps - 1:
                 save_frame(x0, os.path.join(args.out_dir, f"x0_{i}"))
 
-        _, x0 = sample_ddim(model, sampler, cond, audio, shape, generator=g, callback=cb,
-                            guidance_scale=args.guidance_scale,
-                            guidance_rescale=args.guidance_rescale)
+        _, x0 = sample(model, sampler, cond, audio, shape, generator=g, callback=cb,
+                       guidance_scale=args.guidance_scale,
+                       guidance_rescale=args.guidance_rescale)
         print("All images have been processed and saved.")
         return x0
     return sample_images(model, scheduler, cond, audio, n_timesteps=args.steps or 500,
