@@ -359,6 +359,36 @@ typedef struct {            /* 48 bytes */
 int vd_ema_update(const vd_ema_desc* descs, int n_desc, int k, const float* rates, int warmup,
                   const int64_t* num_updates, const int64_t* skip_if_nonneg, void* stream);
 
+/* ---- gradient clipping by global norm (torch.nn.utils.clip_grad_norm_; no reference
+ * counterpart: train.py:102-134 bounds no update) ----
+ * `descs` is a DEVICE array of n_desc descriptors, one per range of an fp32 gradient tensor,
+ * cut by the caller as for vd_ema_update (any number of ranges; blocks walk the table
+ * grid-stride).  A range whose pointer is 16-B aligned moves 8 elements per lane, any other one
+ * element at a time.
+ * vd_grad_sumsq: workspace[i] (fp32, vd_grad_clip_workspace_size(n_desc) bytes) = the sum of
+ * squares of range i in a FIXED order (a lane's fused multiply-add chain, then an LDS tree;
+ * csrc/gradclip.hip states the layout), independent of the grid.
+ * vd_grad_clip: two launches on the same workspace.  One block adds the n_desc partials in one
+ * fixed order (in fp64) and writes
+ *   record[0] = norm = sqrt(total),  record[1] = coef = min(1, max_norm / (norm + 1e-6))
+ * (torch's formula; fp32).  Then every element becomes g * coef (one fp32 multiply) if
+ * coef < 1; with coef == 1 nothing is written.  A non-finite norm records coef = 1 and leaves
+ * every gradient as it is.  max_norm > 0; +inf is legal and means "measure only".
+ * Overflow is NOT scaled away: gradients whose squares overflow fp32 give a non-finite norm,
+ * as torch's do.  No atomics, no memset, no semaphore, no cross-block communication inside a
+ * launch, nothing read on the host: the same bits eager and replayed from a HIP graph.
+ * record: DEVICE fp32[2].  Null pointers, n_desc <= 0, a max_norm that is not > 0 (NaN
+ * included) and a short workspace fail with VD_EINVAL before any launch. */
+typedef struct {            /* 16 bytes */
+  float* g;                 /* fp32 gradient range  */
+  int64_t n;                /* elements in the range */
+} vd_grad_desc;
+size_t vd_grad_clip_workspace_size(int n_desc);
+int vd_grad_sumsq(const vd_grad_desc* descs, int n_desc, void* workspace, size_t workspace_bytes,
+                  void* stream);
+int vd_grad_clip(const vd_grad_desc* descs, int n_desc, const void* workspace, float max_norm,
+                 float* record /* [2]: norm, coef */, void* stream);
+
 /* ---- Flash attention --------------------------------------------------
  * replaces QKVAttentionLegacy.forward (unet.py:349-366) + the fp32 softmax
  * (unet.py:364) and, with heads split by strides, QKVAttention (unet.py:

@@ -50,6 +50,11 @@ class EmaDesc(C.Structure):
     _fields_ = [("src", _vp), ("dst", _vp * 4), ("n", _i64)]
 
 
+class GradDesc(C.Structure):
+    """vd_grad_desc: one range of one fp32 gradient tensor."""
+    _fields_ = [("g", _vp), ("n", _i64)]
+
+
 _SIGS = {
     "vd_version": (_i, []),
     "vd_last_error": (C.c_char_p, []),
@@ -92,6 +97,9 @@ _SIGS = {
     "vd_conv_pack_weight": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "vd_conv_pack_weights": (_i, [_vp, _i, _i64, _i, _vp]),
     "vd_ema_update": (_i, [_vp, _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp]),
+    "vd_grad_clip_workspace_size": (_sz, [_i]),
+    "vd_grad_sumsq": (_i, [_vp, _i, _vp, _sz, _vp]),
+    "vd_grad_clip": (_i, [_vp, _i, _vp, _f, _vp, _vp]),
     "vd_conv_set_wgrad": (_i, [C.c_int]),
     "vd_conv_set_halo": (_i, [_i]),
     "vd_conv3d_fwd": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -221,6 +221,14 @@ class GradBucketer:
         Reads the summed flags: a host synchronisation, for tests and diagnostics only."""
         return [i for i, f in enumerate(self.flags.tolist()) if f == 0]
 
+    def grad_flats(self):
+        """The gradient part of every bucket's flat buffer, in bucket order (read-only use:
+        norms, clipping).  The last bucket's view ends before its "used" flags, which are no
+        gradients: they must never be scaled or counted.  The buffers never move."""
+        last = len(self.buckets) - 1
+        for i, b in enumerate(self.buckets):
+            yield b.flat[:b.flat.numel() - len(self.views)] if i == last else b.flat
+
     def zero_grad(self):
         for b in self.buckets:
             b.flat.zero_()

@@ -32,16 +32,24 @@ _DESC = np.dtype([("src", "<u8"), ("dst", "<u8", (4,)), ("n", "<i8")])
 assert _DESC.itemsize == 48
 
 
-def chunk_ranges(numels, chunk=CHUNK):
-    """[(tensor index, first element, elements)]: every tensor cut into ranges of at most
-    `chunk` elements, in order; no range crosses a tensor and empty tensors get none."""
+def range_arrays(numels, chunk=CHUNK):
+    """The chunk rule as three int64 arrays (tensor index, first element, elements), one entry
+    per range: every tensor cut into ranges of at most `chunk` elements, in order; no range
+    crosses a tensor and empty tensors get none.  No Python loop per range (vdiff.clip rebuilds
+    its table during training)."""
     if chunk <= 0 or chunk % 8:
         raise ValueError(f"chunk {chunk}: a positive multiple of 8")
-    out = []
-    for i, n in enumerate(numels):
-        for s in range(0, int(n), chunk):
-            out.append((i, s, min(chunk, int(n) - s)))
-    return out
+    numels = np.asarray(numels, dtype=np.int64).reshape(-1)
+    counts = -(-numels // chunk)                      # ranges per tensor, 0 for an empty one
+    index = np.repeat(np.arange(len(numels), dtype=np.int64), counts)
+    first_range = np.cumsum(counts) - counts          # a tensor's first range in the table
+    start = (np.arange(len(index), dtype=np.int64) - first_range[index]) * chunk
+    return index, start, np.minimum(chunk, numels[index] - start)
+
+
+def chunk_ranges(numels, chunk=CHUNK):
+    """[(tensor index, first element, elements)]: range_arrays as a list of Python ints."""
+    return list(zip(*(a.tolist() for a in range_arrays(numels, chunk))))
 
 
 def descriptor_rows(src_ptrs, dst_ptrs, numels, chunk=CHUNK):

@@ -81,7 +81,8 @@ class Trainer:
 
     def __init__(self, model, scheduler, lr=1e-2, bucket_mb=25.0, fused_adam=True,
                  check_every=50, batch_pack=True, graph=False, loss_fn=None,
-                 audio_drop_prob=0.0, drop_generator=None, ema_rates=(), ema_warmup=False):
+                 audio_drop_prob=0.0, drop_generator=None, ema_rates=(), ema_warmup=False,
+                 clip_grad_norm=None):
         """check_every: the loss finiteness flag (kept on the device, updated every step) is
         read on the host every `check_every` steps and by check_finite(); a non-finite
         loss raises FloatingPointError naming the first bad step.  0 disables it.
@@ -102,17 +103,33 @@ class Trainer:
         first non-finite loss on, so the averages stay clean until check_finite() raises; with
         check_every=0 there is no record and no such guard.  Under DDP the record is this
         rank's own loss.
-        ema_warmup: decay min(rate, (1 + n) / (10 + n)) after n updates."""
+        ema_warmup: decay min(rate, (1 + n) / (10 + n)) after n updates.
+        clip_grad_norm: None (off: no clipper, no launch, grad_norm is None) or a number > 0, the
+        global L2 norm the step's gradients are clipped to before the optimizer step
+        (vdiff.clip.GradClipper: three launches, fixed summation order, no host sync); inf
+        measures the norm and scales nothing.  Under DDP the averaged gradients are clipped,
+        identically on every rank; in one process a parameter without a gradient is left out.
+        The pre-clip norm and the factor stay on the device (grad_norm, clip_coef).  A
+        non-finite norm scales nothing and counts as a bad step like a non-finite loss: it
+        enters the first-bad-step record, check_finite() names it and the EMA guard holds from
+        that step on.  The optimizer step itself is NOT prevented (fail-fast, as for the loss):
+        the weights of that step are lost, the record says when."""
         if not 0.0 <= audio_drop_prob <= 1.0:
             raise ValueError(f"audio_drop_prob {audio_drop_prob} outside [0, 1]")
         self.audio_drop_prob = float(audio_drop_prob)
         self.drop_generator = drop_generator
         self.model = model
+        self.clipper = None
+        if clip_grad_norm is not None:
+            from .clip import GradClipper, check_max_norm
+            self.clipper = GradClipper(check_max_norm(clip_grad_norm, "clip_grad_norm"))
+        self._bad_grad = None  # device bool: the first bad step had a finite loss (bad norm)
         self.loss_fn = loss_fn or ops.mse_loss
         self.scheduler = scheduler
         self.check_every = int(check_every)
         self.steps_done = 0
         self._first_bad = None  # device int64: first step with a non-finite loss, or -1
+        self._named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         params = [p for p in model.parameters() if p.requires_grad]
         # one process: no all-reduce, so no bucket views -- autograd hands each gradient over
         # without the accumulate-into-view add, and zero_grad drops them (no fills)
@@ -164,15 +181,41 @@ class Trainer:
             loss.backward()
         if self.bucketer is not None:
             self.bucketer.finish()
+            self._clip_grads()
             self.bucketer.step(self.opt)
             self.bucketer.zero_grad()
         else:
+            self._clip_grads()
             self.opt.step()
             self.opt.zero_grad(set_to_none=True)
         loss = loss.detach()
         self._track_finite(loss)
         self._update_ema()
         return loss
+
+    @property
+    def grad_norm(self):
+        """The last step's global gradient norm before clipping (0-dim device view, rewritten
+        by the next step); None without clip_grad_norm."""
+        return None if self.clipper is None else self.clipper.norm
+
+    @property
+    def clip_coef(self):
+        """The last step's clipping factor, 1 where nothing was scaled (0-dim device view)."""
+        return None if self.clipper is None else self.clipper.coef
+
+    def _clip_grads(self):
+        """After backward (and the gradient average under DDP), before the optimizer step."""
+        if self.clipper is None:
+            return
+        if self.bucketer is not None:
+            # the averaged buckets, identical on every rank; a parameter no rank used
+            # contributes its zeros, and the flag tail of the last bucket is left out
+            flats = list(self.bucketer.grad_flats())
+            self.clipper.clip(flats, [f"gradient bucket {i}" for i in range(len(flats))])
+            return
+        named = [(n, p.grad) for n, p in self._named if p.grad is not None]
+        self.clipper.clip([g for _, g in named], [f"the gradient of {n}" for n, _ in named])
 
     def _update_ema(self):
         """After the optimizer step and this step's entry in the first-bad-step record."""
@@ -187,7 +230,16 @@ class Trainer:
             return
         if self._first_bad is None:
             self._first_bad = torch.full((), -1, dtype=torch.int64, device=loss.device)
-        bad = ~torch.isfinite(loss) & (self._first_bad < 0)
+        bad = ~torch.isfinite(loss)
+        if self.clipper is not None and self.clipper.norm is not None:
+            # a finite loss with a non-finite gradient (bf16 backward) is a bad step too
+            bad_norm = ~torch.isfinite(self.clipper.norm)
+            if self._bad_grad is None:
+                self._bad_grad = torch.zeros((), dtype=torch.bool, device=loss.device)
+            first = (bad | bad_norm) & (self._first_bad < 0)
+            self._bad_grad.copy_(torch.where(first, bad_norm & ~bad, self._bad_grad))
+            bad = bad | bad_norm
+        bad = bad & (self._first_bad < 0)
         self._first_bad.copy_(torch.where(bad, self.steps_done, self._first_bad))
         self.steps_done += 1
         if self.steps_done % self.check_every == 0:
@@ -217,7 +269,10 @@ class Trainer:
         else:
             first = int(fb)
         if first >= 0:
-            raise FloatingPointError(f"non-finite training loss at step {first} "
+            what = "training loss"
+            if self._bad_grad is not None and bool(self._bad_grad):
+                what = "gradient norm (the loss was finite)"
+            raise FloatingPointError(f"non-finite {what} at step {first} "
                                      f"(of {self.steps_done})")
 
 
@@ -282,6 +337,7 @@ class TrainStepGraph:
         self.g.replay()
         if enc.requires_grad:
             enc.backward(self.feats.grad)
+        tr._clip_grads()  # eager, like Adam: the graph's static gradients and the encoder's
         tr.opt.step()
         for p in self.eager_params:
             p.grad = None

@@ -791,6 +791,41 @@ def ema_update(table, n_desc, rates, warmup=False, num_updates=None, skip_flag=N
               _p(num_updates), _p(skip_flag), _stream(table))
 
 
+def _grad_table(table, n_desc):
+    _gpu(table)
+    if table.dtype != torch.uint8 or table.numel() < 16 * int(n_desc):
+        raise ValueError(f"descriptor table: uint8 image of {n_desc} vd_grad_desc (16 bytes "
+                         f"each), got {table.dtype} x {table.numel()}")
+
+
+def grad_sumsq(table, n_desc, workspace):
+    """One vd_grad_sumsq launch on the current stream: workspace[i] (fp32 device tensor, at
+    least n_desc elements) = the sum of squares of range i of the device descriptor table
+    `table` (uint8 image of n_desc vd_grad_desc, vdiff.clip builds it), in a fixed order.  No
+    host sync."""
+    _grad_table(table, n_desc)
+    _gpu(workspace)
+    if workspace.dtype != torch.float32:
+        raise TypeError(f"grad_sumsq: fp32 workspace, got {workspace.dtype}")
+    _lib.call("vd_grad_sumsq", _p(table), int(n_desc), _p(workspace), 4 * workspace.numel(),
+              _stream(table))
+
+
+def grad_clip(table, n_desc, workspace, max_norm, record):
+    """vd_grad_clip on the partials grad_sumsq left in `workspace`: record[0] <- the global
+    norm, record[1] <- coef = min(1, max_norm / (norm + 1e-6)), and every element of every
+    range times coef where coef < 1 (two launches, the scalars stay on the device).  record:
+    fp32 device tensor of 2 elements; max_norm > 0, inf measures only."""
+    _grad_table(table, n_desc)
+    _gpu(workspace, record)
+    if workspace.dtype != torch.float32 or record.dtype != torch.float32 or record.numel() < 2:
+        raise TypeError("grad_clip: fp32 workspace and fp32 record[2]")
+    if workspace.numel() < int(n_desc):
+        raise ValueError(f"grad_clip: workspace of {workspace.numel()} partials for {n_desc} ranges")
+    _lib.call("vd_grad_clip", _p(table), int(n_desc), _p(workspace), float(max_norm), _p(record),
+              _stream(table))
+
+
 def channel_sums(x: torch.Tensor) -> torch.Tensor:
     """[B, C, *spatial] channels-last -> fp32 [B, C] sums over the spatial dims."""
     _gpu(x)

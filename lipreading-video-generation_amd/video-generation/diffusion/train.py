@@ -17,6 +17,8 @@ Initialisation is the reference's (zero_module layers included, unet.py:222-224,
 --reinit-nonzero replaces the zero-initialised layers with seeded weights (benchmarks and
 smoke runs only).  --ema-rate R [R ...] keeps exponential moving averages of the weights
 (vdiff.ema) and saves them as <ckpt>.ema_<R>, state dicts that test.py --ckpt loads.
+--clip-grad-norm C clips each step's gradients to the global L2 norm C (vdiff.clip; the
+reference bounds no update) and reports the norm per epoch; 0, the default, leaves it off.
 """
 import argparse
 import os
@@ -77,6 +79,10 @@ def parse(argv=None):
                          "--ckpt (build extension; default: none)")
     ap.add_argument("--ema-warmup", action="store_true",
                     help="EMA decay min(rate, (1 + n) / (10 + n)) after n updates")
+    ap.add_argument("--clip-grad-norm", type=float, default=0.0, metavar="C",
+                    help="clip each step's gradients to the global L2 norm C before the "
+                         "optimizer step (inf: only measure the norm); the epoch line then "
+                         "reports the norm and the clipped steps (build extension; 0 = off)")
     ap.add_argument("--reinit-nonzero", action="store_true",
                     help="seeded weights for the zero-initialised layers (smoke / bench only)")
     return ap.parse_args(argv)
@@ -118,7 +124,8 @@ def train(argv=None):
         drop_gen = torch.Generator(device=device).manual_seed(args.seed * 7919 + rank)
     trainer = Trainer(model, scheduler, lr=args.lr, audio_drop_prob=args.audio_drop_prob,
                       drop_generator=drop_gen, ema_rates=tuple(args.ema_rate),
-                      ema_warmup=args.ema_warmup)
+                      ema_warmup=args.ema_warmup,
+                      clip_grad_norm=args.clip_grad_norm if args.clip_grad_norm != 0 else None)
     start_epoch = 0
     if args.resume:
         state = torch.load(args.resume, map_location=device, weights_only=True)
@@ -145,9 +152,13 @@ def train(argv=None):
                               size=args.image_size, seed=args.seed * world + rank,
                               bug_compatible=not args.fix_audio_resample, dims=args.dims)
     loss = torch.zeros(())
+    clipping = trainer.clipper is not None
     for epoch in range(start_epoch, args.epochs):
         t0 = time.time()
         loss_sum = torch.zeros((), device=device)  # the epoch's mean loss, summed on the device
+        if clipping:  # the epoch's largest gradient norm and its count of clipped steps
+            norm_max = torch.zeros((), device=device)
+            clipped = torch.zeros((), dtype=torch.int64, device=device)
         for step in range(args.steps_per_epoch):
             if batcher is not None:
                 clip = batcher.next()
@@ -157,13 +168,21 @@ def train(argv=None):
                                       seed=(epoch * 1000003 + step) * world + rank, dims=args.dims)
             loss = trainer.step(clip)
             loss_sum += loss
+            if clipping:  # device-side, read once per epoch below
+                torch.maximum(norm_max, trainer.grad_norm, out=norm_max)
+                clipped += trainer.clip_coef < 1
         trainer.check_finite()  # the device-side NaN/Inf record, read once per epoch
         if rank == 0:
             dt = time.time() - t0
             fps = world * args.batch_size * frames * args.steps_per_epoch / dt
+            norms = ""
+            if clipping:
+                norms = (f" | grad norm {trainer.grad_norm.item():.4g} (max {norm_max.item():.4g})"
+                         f" | clipped {int(clipped.item())}/{args.steps_per_epoch} steps")
             # the reference prints the epoch's last loss (train.py:136); the mean is added
             print(f"Finished epoch {epoch + 1} | Loss: {loss.item()} | mean "
-                  f"{loss_sum.item() / args.steps_per_epoch:.5f} | {fps:.2f} frames/s", flush=True)
+                  f"{loss_sum.item() / args.steps_per_epoch:.5f}{norms} | {fps:.2f} frames/s",
+                  flush=True)
             torch.save(model.state_dict(), args.ckpt)
             resume = {"model": model.state_dict(), "optimizer": trainer.opt.state_dict(),
                       "epoch": epoch}
