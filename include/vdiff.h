@@ -389,6 +389,61 @@ int vd_grad_sumsq(const vd_grad_desc* descs, int n_desc, void* workspace, size_t
 int vd_grad_clip(const vd_grad_desc* descs, int n_desc, const void* workspace, float max_norm,
                  float* record /* [2]: norm, coef */, void* stream);
 
+/* ---- Adam / AdamW step (torch.optim.Adam / AdamW's update; train.py:102 is Adam at a constant
+ * rate) with the learning-rate schedule and the bad-step decision taken ON THE DEVICE ----
+ * `descs` is a DEVICE array of n_desc descriptors, one per range of one parameter tensor (cut by
+ * the caller as for vd_ema_update; the ranges of one tensor are consecutive rows).  Two launches
+ * whatever the number of tensors; no atomics, no memset, no semaphore, nothing read on the host:
+ * the same bits eager and replayed from a HIP graph.
+ * Launch 1 (grid-stride over the table) updates p, m, v of every range from g.  A range whose
+ * four pointers are 16-B aligned moves 8 elements per lane, any other one element at a time.
+ * Every block reads the same device words, none of which launch 1 writes:
+ *   steps[tensor]             the tensor's own count of applied updates (t = count + 1)
+ *   state[0..3]               applied, skipped, run (consecutive skipped), tripped_at (-1: not)
+ *   loss, grad_norm           fp32 scalars, either may be NULL
+ * The step is SKIPPED -- launch 1 writes nothing -- if max_bad_run > 0 and (loss is non-finite
+ * or grad_norm is non-finite or tripped_at >= 0).  Otherwise, with s = applied:
+ *   lr_s = lr * warm(s) * decay(s);  warm = min(1, (s + 1) / W) (W = 0: 1);
+ *   q = clamp((s - W) / (T - W), 0, 1);  decay = 1 (VD_LR_CONSTANT)
+ *     | r + (1 - r) (1 + cos(pi q)) / 2 (VD_LR_COSINE) | r + (1 - r) (1 - q) (VD_LR_LINEAR)
+ *   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t          (lr_s, bc1, bc2 in fp64, rounded to fp32 once)
+ *   g' = g + wd p (L2 mode);  m += (1 - beta1)(g' - m);  v = beta2 v + (1 - beta2) g' g';
+ *   p *= 1 - lr_s wd (decoupled mode);  p -= (lr_s / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * (csrc/adam.hip states the exact fp32 operation order).
+ * Launch 2 (one block) takes the same decision from the same words, then: applied step --
+ * steps[tensor] += 1 for every tensor of the table, applied += 1, run = 0; skipped step --
+ * skipped += 1, run += 1, and if run > max_bad_run and tripped_at < 0, tripped_at = the global
+ * step index (applied + skipped before this step; sticky: every later step is skipped).  It
+ * records lr_out[0] = lr_s of this step (at the unchanged s on a skipped step) and
+ * skip_flag_out[0] = -1 (applied) or the global step index (skipped), the convention of
+ * vd_ema_update's skip_if_nonneg.
+ * The hyperparameters are HOST values passed per launch: a captured launch freezes them.
+ * Null descs / h / steps / state / lr_out / skip_flag_out, n_desc <= 0, a beta outside [0, 1),
+ * eps <= 0, a negative lr or weight_decay, total_steps <= warmup_steps with a non-constant
+ * schedule, min_ratio outside [0, 1], an unknown schedule and negative warmup_steps or
+ * max_bad_run fail with VD_EINVAL before any launch. */
+enum vd_lr_schedule { VD_LR_CONSTANT = 0, VD_LR_COSINE = 1, VD_LR_LINEAR = 2 };
+typedef struct {            /* 48 bytes */
+  float* p;                 /* fp32 parameter range                          */
+  float* m;                 /* its first moment (exp_avg)                    */
+  float* v;                 /* its second moment (exp_avg_sq)                */
+  const float* g;           /* its gradient                                  */
+  int64_t n;                /* elements in the range                         */
+  int64_t tensor;           /* the tensor's index into the step-count array  */
+} vd_adam_desc;
+typedef struct {            /* 80 bytes */
+  double lr, beta1, beta2, eps, weight_decay, min_ratio;
+  int64_t warmup_steps;     /* W */
+  int64_t total_steps;      /* T (ignored by VD_LR_CONSTANT) */
+  int32_t schedule;         /* vd_lr_schedule */
+  int32_t decoupled;        /* 1: AdamW's decay of p, 0: L2 (wd p added to g) */
+  int32_t max_bad_run;      /* K; 0: never skip */
+  int32_t reserved;
+} vd_adam_hyper;
+int vd_adam_step(const vd_adam_desc* descs, int n_desc, const vd_adam_hyper* h, int64_t* steps,
+                 int64_t* state /* [4] */, const float* loss, const float* grad_norm,
+                 float* lr_out, int64_t* skip_flag_out, void* stream);
+
 /* ---- Flash attention --------------------------------------------------
  * replaces QKVAttentionLegacy.forward (unet.py:349-366) + the fp32 softmax
  * (unet.py:364) and, with heads split by strides, QKVAttention (unet.py:

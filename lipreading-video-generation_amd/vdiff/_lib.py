@@ -55,6 +55,19 @@ class GradDesc(C.Structure):
     _fields_ = [("g", _vp), ("n", _i64)]
 
 
+class AdamDesc(C.Structure):
+    """vd_adam_desc: one range of a parameter, its two moments and its gradient."""
+    _fields_ = [("p", _vp), ("m", _vp), ("v", _vp), ("g", _vp), ("n", _i64), ("tensor", _i64)]
+
+
+class AdamHyper(C.Structure):
+    """vd_adam_hyper: the host-side hyperparameters of one vd_adam_step."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("min_ratio", C.c_double),
+                ("warmup_steps", _i64), ("total_steps", _i64), ("schedule", C.c_int32),
+                ("decoupled", C.c_int32), ("max_bad_run", C.c_int32), ("reserved", C.c_int32)]
+
+
 _SIGS = {
     "vd_version": (_i, []),
     "vd_last_error": (C.c_char_p, []),
@@ -100,6 +113,7 @@ _SIGS = {
     "vd_grad_clip_workspace_size": (_sz, [_i]),
     "vd_grad_sumsq": (_i, [_vp, _i, _vp, _sz, _vp]),
     "vd_grad_clip": (_i, [_vp, _i, _vp, _f, _vp, _vp]),
+    "vd_adam_step": (_i, [_vp, _i, C.POINTER(AdamHyper), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "vd_conv_set_wgrad": (_i, [C.c_int]),
     "vd_conv_set_halo": (_i, [_i]),
     "vd_conv3d_fwd": (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

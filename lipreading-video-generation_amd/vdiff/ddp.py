@@ -194,12 +194,13 @@ class GradBucketer:
             self._times.append((e0, e1))
 
     @torch.no_grad()
-    def step(self, optimizer):
-        """optimizer.step(), except that parameters no rank produced a gradient for keep
-        their values and optimizer state (as with .grad = None in one process).  Call after
-        finish()."""
+    def step(self, optimizer, **step_args):
+        """optimizer.step(**step_args), except that parameters no rank produced a gradient for
+        keep their values and optimizer state (as with .grad = None in one process).  Call
+        after finish().  step_args: what the optimizer reads on the device
+        (vdiff.optim.FusedAdamW's grad_norm); they must be identical on every rank."""
         if self.world == 1 or not self.unused_local:
-            optimizer.step()
+            optimizer.step(**step_args)
             return
         snaps = []
         for i in self.unused_local:
@@ -207,7 +208,7 @@ class GradBucketer:
             st = optimizer.state.get(p, {})
             snaps.append((i, p, p.detach().clone(),
                           {k: v.clone() for k, v in st.items() if torch.is_tensor(v)}))
-        optimizer.step()
+        optimizer.step(**step_args)
         for i, p, p0, s0 in snaps:
             keep = self.flags[i] > 0  # summed over ranks: used somewhere
             p.copy_(torch.where(keep, p, p0))

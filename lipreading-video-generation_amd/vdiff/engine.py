@@ -82,7 +82,9 @@ class Trainer:
     def __init__(self, model, scheduler, lr=1e-2, bucket_mb=25.0, fused_adam=True,
                  check_every=50, batch_pack=True, graph=False, loss_fn=None,
                  audio_drop_prob=0.0, drop_generator=None, ema_rates=(), ema_warmup=False,
-                 clip_grad_norm=None):
+                 clip_grad_norm=None, optimizer="torch", weight_decay=0.0,
+                 decoupled_weight_decay=True, lr_warmup=0, lr_schedule="constant",
+                 lr_total_steps=None, lr_min_ratio=0.0, skip_bad_steps=0):
         """check_every: the loss finiteness flag (kept on the device, updated every step) is
         read on the host every `check_every` steps and by check_finite(); a non-finite
         loss raises FloatingPointError naming the first bad step.  0 disables it.
@@ -113,7 +115,27 @@ class Trainer:
         non-finite norm scales nothing and counts as a bad step like a non-finite loss: it
         enters the first-bad-step record, check_finite() names it and the EMA guard holds from
         that step on.  The optimizer step itself is NOT prevented (fail-fast, as for the loss):
-        the weights of that step are lost, the record says when."""
+        the weights of that step are lost, the record says when.
+        optimizer: "torch" (the default: torch.optim.Adam at the constant rate lr, exactly as
+        before) or "hip" (vdiff.optim.FusedAdamW: two launches per step, the schedule and the
+        bad-step decision on the device).  The seven options below need "hip"; a non-default
+        value with "torch" raises ValueError.
+        weight_decay, decoupled_weight_decay: AdamW's decay (True) or Adam's L2 (False).
+        lr_warmup, lr_schedule, lr_total_steps, lr_min_ratio: linear warm-up over lr_warmup
+        steps, then "constant", or "cosine" / "linear" decay to lr_min_ratio * lr at
+        lr_total_steps.  The position is the device count of APPLIED steps; self.lr is the rate
+        of the last step (0-dim device view).
+        skip_bad_steps: K > 0 makes a step whose loss (one process) or gradient norm (with
+        clip_grad_norm, any world size) is non-finite a SKIPPED step: the kernels write nothing,
+        so weights, moments and counts keep their bits, and the EMA holds still for that step
+        only.  The sticky first-bad-step record is not written; self.skipped_steps counts (0-dim
+        device view).  More than K skipped steps in a row trip the optimizer -- every later step
+        is skipped too, the weights stay those of the last good step -- and check_finite()
+        raises FloatingPointError naming the step.  Under DDP the decision must be identical on
+        every rank, so only the norm of the averaged gradients decides (bit-identical
+        everywhere; a rank-local loss would let the ranks diverge): clip_grad_norm is required
+        there.  Without clip_grad_norm (inf measures only) nothing guards against a non-finite
+        gradient behind a finite loss.  K = 0 keeps the fail-fast record above exactly."""
         if not 0.0 <= audio_drop_prob <= 1.0:
             raise ValueError(f"audio_drop_prob {audio_drop_prob} outside [0, 1]")
         self.audio_drop_prob = float(audio_drop_prob)
@@ -134,9 +156,35 @@ class Trainer:
         # one process: no all-reduce, so no bucket views -- autograd hands each gradient over
         # without the accumulate-into-view add, and zero_grad drops them (no fills)
         distributed = torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        if (optimizer == "hip" and distributed and self.clipper is None
+                and isinstance(skip_bad_steps, int) and skip_bad_steps > 0):
+            raise ValueError("Trainer(skip_bad_steps > 0) under DDP needs clip_grad_norm "
+                             "(inf measures only): the ranks must take the same decision, and "
+                             "only the averaged gradients' norm is identical on all of them")
         self.bucketer = GradBucketer(params, bucket_mb) if distributed else None
-        kw = {"fused": True} if fused_adam and params and params[0].is_cuda else {}
-        self.opt = torch.optim.Adam(params, lr=lr, **kw)
+        if optimizer not in ("torch", "hip"):
+            raise ValueError(f"optimizer {optimizer!r}: 'torch' or 'hip'")
+        self.hip_opt = optimizer == "hip"
+        self.skip_bad_steps = 0
+        if self.hip_opt:
+            from .optim import FusedAdamW
+            self.opt = FusedAdamW(params, lr=lr, weight_decay=weight_decay,
+                                  decoupled=decoupled_weight_decay, warmup_steps=lr_warmup,
+                                  schedule=lr_schedule, total_steps=lr_total_steps,
+                                  min_ratio=lr_min_ratio, max_bad_run=skip_bad_steps)
+            self.skip_bad_steps = int(skip_bad_steps)
+        else:
+            given = dict(weight_decay=(weight_decay, 0.0),
+                         decoupled_weight_decay=(decoupled_weight_decay, True),
+                         lr_warmup=(lr_warmup, 0), lr_schedule=(lr_schedule, "constant"),
+                         lr_total_steps=(lr_total_steps, None), lr_min_ratio=(lr_min_ratio, 0.0),
+                         skip_bad_steps=(skip_bad_steps, 0))
+            extra = [k for k, (v, d) in given.items() if v != d]
+            if extra:
+                raise ValueError(f"Trainer({', '.join(extra)}) needs optimizer='hip' "
+                                 "(torch.optim.Adam runs at a constant rate without decay)")
+            kw = {"fused": True} if fused_adam and params and params[0].is_cuda else {}
+            self.opt = torch.optim.Adam(params, lr=lr, **kw)
         # conv operands re-packed once per step in one launch (ops.step_packed_weights)
         self.packs = ops.step_packed_weights() if batch_pack else contextlib.nullcontext()
         if graph and self.bucketer is not None:
@@ -182,11 +230,12 @@ class Trainer:
         if self.bucketer is not None:
             self.bucketer.finish()
             self._clip_grads()
-            self.bucketer.step(self.opt)
+            # DDP: the norm only (identical on every rank), never this rank's own loss
+            self.bucketer.step(self.opt, **self._opt_args(None))
             self.bucketer.zero_grad()
         else:
             self._clip_grads()
-            self.opt.step()
+            self.opt.step(**self._opt_args(loss.detach()))
             self.opt.zero_grad(set_to_none=True)
         loss = loss.detach()
         self._track_finite(loss)
@@ -204,6 +253,26 @@ class Trainer:
         """The last step's clipping factor, 1 where nothing was scaled (0-dim device view)."""
         return None if self.clipper is None else self.clipper.coef
 
+    @property
+    def lr(self):
+        """The last step's learning rate (0-dim fp32 device view, rewritten by the next step);
+        None with optimizer="torch"."""
+        return self.opt.lr if self.hip_opt else None
+
+    @property
+    def skipped_steps(self):
+        """Steps skipped so far (0-dim int64 device view); None with optimizer="torch"."""
+        return self.opt.skipped if self.hip_opt else None
+
+    def _opt_args(self, loss):
+        """What the optimizer step reads on the device: nothing for torch's Adam; for FusedAdamW
+        the loss (None under DDP) and, with a clipper, the gradient norm."""
+        if not self.hip_opt:
+            return {}
+        if loss is not None and loss.dtype != torch.float32:
+            loss = loss.float()
+        return {"loss": loss, "grad_norm": None if self.clipper is None else self.clipper.norm}
+
     def _clip_grads(self):
         """After backward (and the gradient average under DDP), before the optimizer step."""
         if self.clipper is None:
@@ -220,13 +289,20 @@ class Trainer:
     def _update_ema(self):
         """After the optimizer step and this step's entry in the first-bad-step record."""
         if self.ema is not None:
-            self.ema.update(skip_flag=self._first_bad)
+            # skip mode: still on the skipped steps only; else from the first bad step on
+            self.ema.update(skip_flag=self.opt.skip_flag if self.skip_bad_steps > 0
+                            else self._first_bad)
 
     def _track_finite(self, loss):
         """SURVEY 5 failure detection without a per-step host sync: a device-side record of
         the first step whose loss is NaN/Inf (the reference skips nothing and checks
         nothing, train.py:111-112), read every check_every steps."""
         if self.check_every <= 0:
+            return
+        if self.skip_bad_steps > 0:  # the optimizer's device words are the record
+            self.steps_done += 1
+            if self.steps_done % self.check_every == 0:
+                self.check_finite()
             return
         if self._first_bad is None:
             self._first_bad = torch.full((), -1, dtype=torch.int64, device=loss.device)
@@ -252,6 +328,16 @@ class Trainer:
         the ranks first, so a loss that went non-finite on one rank makes EVERY rank raise
         here together instead of leaving the others blocked in the next gradient
         all-reduce (advisor r03).  Every rank reaches this call at the same step count."""
+        if self.skip_bad_steps > 0:
+            # identical on every rank (the decision reads the averaged gradients' norm only)
+            at = int(self.opt.tripped_at)
+            if at >= 0:
+                raise FloatingPointError(
+                    f"more than {self.skip_bad_steps} consecutive steps with a non-finite loss "
+                    f"or gradient norm: tripped at step {at} (of {self.steps_done}), "
+                    f"{int(self.opt.skipped)} steps skipped; the weights are those of the last "
+                    "good step")
+            return
         if self._first_bad is None and self.bucketer is None:
             return
         if self._first_bad is None:
@@ -338,7 +424,7 @@ class TrainStepGraph:
         if enc.requires_grad:
             enc.backward(self.feats.grad)
         tr._clip_grads()  # eager, like Adam: the graph's static gradients and the encoder's
-        tr.opt.step()
+        tr.opt.step(**tr._opt_args(self.loss))  # (the replay's loss, read on the device)
         for p in self.eager_params:
             p.grad = None
         self.steps += 1

@@ -826,6 +826,50 @@ def grad_clip(table, n_desc, workspace, max_norm, record):
               _stream(table))
 
 
+LR_SCHEDULES = {"constant": 0, "cosine": 1, "linear": 2}   # vd_lr_schedule
+
+
+def adam_hyper(lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True,
+               warmup_steps=0, schedule="constant", total_steps=None, min_ratio=0.0,
+               max_bad_run=0):
+    """The vd_adam_hyper of one launch pair (host values; the library checks their ranges)."""
+    if schedule not in LR_SCHEDULES:
+        raise ValueError(f"schedule {schedule!r}: one of {sorted(LR_SCHEDULES)}")
+    h = _lib.AdamHyper()
+    h.lr, h.beta1, h.beta2 = float(lr), float(betas[0]), float(betas[1])
+    h.eps, h.weight_decay, h.min_ratio = float(eps), float(weight_decay), float(min_ratio)
+    h.warmup_steps = int(warmup_steps)
+    h.total_steps = 0 if total_steps is None else int(total_steps)
+    h.schedule, h.decoupled = LR_SCHEDULES[schedule], int(bool(decoupled))
+    h.max_bad_run = int(max_bad_run)
+    return h
+
+
+def adam_step(table, n_desc, hyper, steps, state, lr_out, skip_flag_out, loss=None,
+              grad_norm=None):
+    """vd_adam_step on the current stream: the Adam / AdamW update of every range of the device
+    descriptor table `table` (uint8 image of n_desc vd_adam_desc, vdiff.optim builds it), then
+    the one-block advance of the counts and the record (two launches, no host sync).
+    hyper: adam_hyper(...).  steps: int64 device array the table's tensor indices point into.
+    state: int64 device [applied, skipped, run, tripped_at].  lr_out: fp32 device scalar,
+    skip_flag_out: int64 device scalar (the record).  loss / grad_norm: fp32 device scalars the
+    kernels test for finiteness when hyper.max_bad_run > 0, or None."""
+    _gpu(table, steps, state, lr_out, skip_flag_out, loss, grad_norm)
+    if table.dtype != torch.uint8 or table.numel() < 48 * int(n_desc):
+        raise ValueError(f"descriptor table: uint8 image of {n_desc} vd_adam_desc (48 bytes "
+                         f"each), got {table.dtype} x {table.numel()}")
+    for t in (steps, state, skip_flag_out):
+        if t.dtype != torch.int64:
+            raise TypeError(f"adam_step: int64 counts, state and skip flag, got {t.dtype}")
+    if state.numel() < 4:
+        raise ValueError(f"adam_step: state of 4 int64 words, got {state.numel()}")
+    for t in (lr_out, loss, grad_norm):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"adam_step: fp32 device scalars (loss, grad_norm, lr), got {t.dtype}")
+    _lib.call("vd_adam_step", _p(table), int(n_desc), _lib.C.byref(hyper), _p(steps), _p(state),
+              _p(loss), _p(grad_norm), _p(lr_out), _p(skip_flag_out), _stream(table))
+
+
 def channel_sums(x: torch.Tensor) -> torch.Tensor:
     """[B, C, *spatial] channels-last -> fp32 [B, C] sums over the spatial dims."""
     _gpu(x)

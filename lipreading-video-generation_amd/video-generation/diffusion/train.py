@@ -19,6 +19,10 @@ smoke runs only).  --ema-rate R [R ...] keeps exponential moving averages of the
 (vdiff.ema) and saves them as <ckpt>.ema_<R>, state dicts that test.py --ckpt loads.
 --clip-grad-norm C clips each step's gradients to the global L2 norm C (vdiff.clip; the
 reference bounds no update) and reports the norm per epoch; 0, the default, leaves it off.
+--optimizer hip replaces torch.optim.Adam by vdiff.optim.FusedAdamW (two launches per step) and
+enables --weight-decay, --lr-warmup, --lr-schedule, --lr-min-ratio and --skip-bad-steps; the
+epoch line then reports the current learning rate and the skipped steps.  Checkpoints written
+under either optimizer resume under the other.
 """
 import argparse
 import os
@@ -83,6 +87,25 @@ def parse(argv=None):
                     help="clip each step's gradients to the global L2 norm C before the "
                          "optimizer step (inf: only measure the norm); the epoch line then "
                          "reports the norm and the clipped steps (build extension; 0 = off)")
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "hip"],
+                    help="torch: torch.optim.Adam(fused) at the constant rate --lr (the "
+                         "default); hip: vdiff.optim.FusedAdamW, needed by the five options "
+                         "below (build extension)")
+    ap.add_argument("--weight-decay", type=float, default=0.0,
+                    help="AdamW's decoupled weight decay (--optimizer hip)")
+    ap.add_argument("--lr-warmup", type=int, default=0, metavar="N",
+                    help="linear warm-up of the learning rate over the first N applied steps "
+                         "(--optimizer hip)")
+    ap.add_argument("--lr-schedule", default="constant", choices=["constant", "cosine", "linear"],
+                    help="decay of the learning rate after the warm-up, to --lr-min-ratio * lr "
+                         "at epochs * steps-per-epoch steps (--optimizer hip)")
+    ap.add_argument("--lr-min-ratio", type=float, default=0.0,
+                    help="final learning rate of the cosine / linear schedule as a share of --lr")
+    ap.add_argument("--skip-bad-steps", type=int, default=0, metavar="K",
+                    help="skip a step whose loss or gradient norm is non-finite (weights, "
+                         "moments and EMA keep their bits) and stop only after more than K in a "
+                         "row; 0 fails at the first one (--optimizer hip; with several GPUs also "
+                         "--clip-grad-norm, inf to measure only)")
     ap.add_argument("--reinit-nonzero", action="store_true",
                     help="seeded weights for the zero-initialised layers (smoke / bench only)")
     return ap.parse_args(argv)
@@ -125,7 +148,12 @@ def train(argv=None):
     trainer = Trainer(model, scheduler, lr=args.lr, audio_drop_prob=args.audio_drop_prob,
                       drop_generator=drop_gen, ema_rates=tuple(args.ema_rate),
                       ema_warmup=args.ema_warmup,
-                      clip_grad_norm=args.clip_grad_norm if args.clip_grad_norm != 0 else None)
+                      clip_grad_norm=args.clip_grad_norm if args.clip_grad_norm != 0 else None,
+                      optimizer=args.optimizer, weight_decay=args.weight_decay,
+                      lr_warmup=args.lr_warmup, lr_schedule=args.lr_schedule,
+                      lr_total_steps=(args.epochs * args.steps_per_epoch
+                                      if args.lr_schedule != "constant" else None),
+                      lr_min_ratio=args.lr_min_ratio, skip_bad_steps=args.skip_bad_steps)
     start_epoch = 0
     if args.resume:
         state = torch.load(args.resume, map_location=device, weights_only=True)
@@ -179,6 +207,9 @@ def train(argv=None):
             if clipping:
                 norms = (f" | grad norm {trainer.grad_norm.item():.4g} (max {norm_max.item():.4g})"
                          f" | clipped {int(clipped.item())}/{args.steps_per_epoch} steps")
+            if trainer.lr is not None:  # --optimizer hip: the device record, read once per epoch
+                norms += (f" | lr {trainer.lr.item():.4g}"
+                          f" | skipped {int(trainer.skipped_steps.item())} steps")
             # the reference prints the epoch's last loss (train.py:136); the mean is added
             print(f"Finished epoch {epoch + 1} | Loss: {loss.item()} | mean "
                   f"{loss_sum.item() / args.steps_per_epoch:.5f}{norms} | {fps:.2f} frames/s",
