@@ -81,6 +81,38 @@ int vd_mse_loss(const void* pred, const void* target, int64_t n, int dtype, floa
 int vd_mse_loss_bwd(const void* pred, const void* target, const float* grad_loss, int64_t n,
                     int dtype, void* grad_pred, void* stream);
 
+/* ---- training objective: v-prediction and Min-SNR weighting (build extension; the reference
+ * trains noise prediction with the unweighted MSE above) ----
+ * Per sample b, with i = t[b] clamped into [0, T - 1], sa = sqrt_acp[i], s1m = sqrt_1m_acp[i]
+ * (the tables vd_q_sample reads) and snr = (sa / s1m)^2:
+ *   target  VD_PRED_EPS: eps;  VD_PRED_V: sa eps - s1m x0 (Salimans & Ho 2022), formed in
+ *           registers, never written to memory;
+ *   w_b     VD_WEIGHT_NONE: 1;  VD_WEIGHT_MIN_SNR (Hang et al. 2023): min(snr, gamma) / snr for
+ *           eps, min(snr, gamma) / (snr + 1) for v;
+ *   per_sample_mse[b] = 1 / P sum_i (pred - target)^2 (unweighted, fp32 [B]);
+ *   loss[0] = 1 / B sum_b w_b per_sample_mse[b] (fp32).
+ * pred, x0, eps: [B][per_sample] in `dtype` (x0 is not read for VD_PRED_EPS and may be NULL);
+ * t: int64[B] on the device; B <= 65535.  vd_diffusion_loss is a FIXED-order reduction built to
+ * the rules of vd_mse_loss / vd_cfg_stats: block k of sample b sums one fixed contiguous range
+ * into workspace[b][k] (vd_diffusion_loss_workspace_size bytes), then one block adds each
+ * sample's partials in block order and the weighted samples in sample order.  Two launches, no
+ * atomics, no memset, no semaphore: the same bits eager and replayed from a HIP graph.
+ * vd_diffusion_loss_bwd: grad_pred = grad_loss[0] 2 w_b / (B P) (pred - target) in `dtype`
+ * (grad_loss: device fp32 scalar); one launch, target and w_b recomputed. */
+enum vd_prediction { VD_PRED_EPS = 0, VD_PRED_V = 1 };
+enum vd_loss_weighting { VD_WEIGHT_NONE = 0, VD_WEIGHT_MIN_SNR = 1 };
+size_t vd_diffusion_loss_workspace_size(int64_t B, int64_t per_sample);
+int vd_diffusion_loss(const void* pred, const void* x0, const void* eps, const int64_t* t,
+                      const float* sqrt_acp, const float* sqrt_1m_acp, int64_t T,
+                      int prediction, int weighting, float gamma, int64_t B,
+                      int64_t per_sample, int dtype, float* loss, float* per_sample_mse,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int vd_diffusion_loss_bwd(const void* pred, const void* x0, const void* eps, const int64_t* t,
+                          const float* sqrt_acp, const float* sqrt_1m_acp, int64_t T,
+                          int prediction, int weighting, float gamma, const float* grad_loss,
+                          int64_t B, int64_t per_sample, int dtype, void* grad_pred,
+                          void* stream);
+
 /* p_sample V1: linear_noise_scheduler.py:48-76 (LinearNoiseScheduler.
  * sample_prev_timestep).  x0 = clamp((xt - s1m[t] eps) / sqrt(acp[t])),
  * mean = (xt - beta[t] eps / s1m[t]) / sqrt(alpha[t]); t == 0 returns mean,
@@ -119,6 +151,15 @@ int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev,
                  void* x0, const int64_t* t, const int64_t* t_prev,
                  const float* acp, float eta, int clip, int64_t B,
                  int64_t per_sample, int dtype, void* stream);
+/* The same step for a model output of either parameterisation (enum vd_prediction, above).
+ * VD_PRED_EPS: vd_ddim_step's own kernel, the same bits.  VD_PRED_V: `eps` holds the model's v
+ * and, with sa = sqrt(a_t), s1m = sqrt(1 - a_t),
+ *   x0 = sa xt - s1m v,  eps = s1m xt + sa v;
+ * the clamp, the direction and the noise terms are as above. */
+int vd_ddim_step_pred(const void* xt, const void* eps, const void* z, void* x_prev,
+                      void* x0, const int64_t* t, const int64_t* t_prev,
+                      const float* acp, float eta, int clip, int prediction, int64_t B,
+                      int64_t per_sample, int dtype, void* stream);
 
 /* ---- classifier-free audio guidance (build extension; no reference counterpart: the
  * reference samples with one conditional forward per step, test.py:51-83) ----
@@ -151,6 +192,15 @@ int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const
 int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w, float rescale,
                    const void* workspace, int64_t B, int64_t per_sample, int dtype,
                    void* stream);
+/* vd_ddim_step_cfg for either parameterisation: the guide and the std-rescale act on the model
+ * output -- with VD_PRED_V on the two v outputs, as Lin et al. define the rescale -- and the
+ * guided output enters the step as in vd_ddim_step_pred.  VD_PRED_EPS: vd_ddim_step_cfg's own
+ * kernel, the same bits. */
+int vd_ddim_step_cfg_pred(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                          void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                          const int64_t* t_prev, const float* acp, float w, float rescale,
+                          const void* workspace, float eta, int clip, int prediction,
+                          int64_t B, int64_t per_sample, int dtype, void* stream);
 
 /* DPM-Solver++(2M) step (Lu et al. 2022; build extension, no reference counterpart): a
  * second-order multistep update that reuses the previous step's x0 instead of a second forward.
@@ -166,7 +216,10 @@ int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w,
  * vd_dpm_step_cfg: guide, rescale and the same update in one pass, as vd_ddim_step_cfg: eps =
  * f_b (eps_u + w (eps_c - eps_u)); x_prev_dup (may be NULL) receives x_prev's values too;
  * rescale > 0 reads the vd_cfg_stats workspace, rescale == 0 accepts a NULL one.
- * Plain vector loads and stores: no atomics, no memset, no LDS beyond the f_b sum. */
+ * Plain vector loads and stores: no atomics, no memset, no LDS beyond the f_b sum.
+ * v-prediction needs no other kernel: x0 = alpha xt - sigma v = (xt - (sigma / alpha) v) / (1 /
+ * alpha), so a table whose columns 0 and 1 hold 1 / alpha_t and sigma_t / alpha_t
+ * (DPMSolverSampler(prediction="v")) makes `eps` the model's v, guided or not. */
 int vd_dpm_step(const void* xt, const void* eps, void* x_prev, void* x0_hist,
                 const float* coef, int64_t n_steps, const int64_t* step, int clip,
                 int64_t B, int64_t per_sample, int dtype, void* stream);

@@ -107,6 +107,10 @@ struct DDIMStep {
   int clip;
   int has_z;
   // b index is passed through tb via the high bits? no: operator gets tb and b.
+  // PRED_V: `eps` holds the model's v (Salimans & Ho 2022): x0 = sqrt(a_t) xt - sqrt(1 - a_t) v,
+  // eps = sqrt(1 - a_t) xt + sqrt(a_t) v; clip, direction and noise terms are the same.  The
+  // eps instantiation is the code it was before the template parameter: the same bits.
+  template <bool PRED_V>
   __device__ void run(int64_t tb, int64_t tp, const float* xt, const float* eps, const float* z,
                       float* xprev, float* x0o, int n) const {
     const float at = acp[tb];
@@ -116,12 +120,22 @@ struct DDIMStep {
     const float dir = sqrtf(fmaxf(1.f - ap - sigma * sigma, 0.f));
     const float sq_ap = sqrtf(ap);
     for (int i = 0; i < n; ++i) {
-      float x0 = (xt[i] - sq_1mat * eps[i]) / sq_at;
-      if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-      x0o[i] = x0;
-      float v = sq_ap * x0 + dir * eps[i];
-      if (has_z) v += sigma * z[i];
-      xprev[i] = v;
+      if constexpr (PRED_V) {
+        float x0 = sq_at * xt[i] - sq_1mat * eps[i];
+        const float e = sq_1mat * xt[i] + sq_at * eps[i];
+        if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+        x0o[i] = x0;
+        float v = sq_ap * x0 + dir * e;
+        if (has_z) v += sigma * z[i];
+        xprev[i] = v;
+      } else {
+        float x0 = (xt[i] - sq_1mat * eps[i]) / sq_at;
+        if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+        x0o[i] = x0;
+        float v = sq_ap * x0 + dir * eps[i];
+        if (has_z) v += sigma * z[i];
+        xprev[i] = v;
+      }
     }
   }
 };
@@ -163,7 +177,7 @@ __global__ void sched_kernel(Op op, const T* __restrict__ a, const T* __restrict
   }
 }
 
-template <typename T, int VEC>
+template <typename T, int VEC, bool PRED_V>
 __global__ void ddim_kernel(DDIMStep op, const T* __restrict__ xt, const T* __restrict__ eps,
                             const T* __restrict__ z, T* __restrict__ xprev, T* __restrict__ x0,
                             const int64_t* __restrict__ t, int64_t B, int64_t per_sample) {
@@ -176,7 +190,7 @@ __global__ void ddim_kernel(DDIMStep op, const T* __restrict__ xt, const T* __re
     ld_vec(xt + e, xa, VEC);
     ld_vec(eps + e, xb, VEC);
     if (z) ld_vec(z + e, xc, VEC);
-    op.run(t[bi], op.tprev[bi], xa, xb, xc, y0, y1, VEC);
+    op.run<PRED_V>(t[bi], op.tprev[bi], xa, xb, xc, y0, y1, VEC);
     st_vec(xprev + e, y0, VEC);
     if (x0) st_vec(x0 + e, y1, VEC);
   }
@@ -470,7 +484,7 @@ __device__ __forceinline__ float cfg_factor(const float* __restrict__ part, int6
 // Guide + rescale + DDIM step in one pass: reads xt, c, u (and z), writes x_prev (twice when
 // xdup is given: the graph sampler's doubled-batch input) and x0.  blockIdx.y = sample, so a
 // block takes f_b once; x_prev may alias xt (a lane reads its elements before it writes them).
-template <typename T, int VEC>
+template <typename T, int VEC, bool PRED_V>
 __global__ void __launch_bounds__(kBlock) cfg_ddim_kernel(
     DDIMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
     const T* __restrict__ z, T* xprev, T* xdup, T* __restrict__ x0,
@@ -491,7 +505,7 @@ __global__ void __launch_bounds__(kBlock) cfg_ddim_kernel(
     ld_vec(u + e, xu, VEC);
     if (z) ld_vec(z + e, xz, VEC);
     gd.run(xc, xu, f, scale, g, VEC);
-    op.run(tb, tp, xa, g, xz, y0, y1, VEC);
+    op.run<PRED_V>(tb, tp, xa, g, xz, y0, y1, VEC);
     st_vec(xprev + e, y0, VEC);
     if (xdup) st_vec(xdup + e, y0, VEC);
     if (x0) st_vec(x0 + e, y1, VEC);
@@ -1078,23 +1092,40 @@ int vd_p_sample_cosine(const void* xt, const void* eps, const void* z, void* x_p
                       per_sample, dtype, stream);
 }
 
-int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev, void* x0,
-                 const int64_t* t, const int64_t* t_prev, const float* acp, float eta, int clip,
-                 int64_t B, int64_t per_sample, int dtype, void* stream) {
+int vd_ddim_step_pred(const void* xt, const void* eps, const void* z, void* x_prev, void* x0,
+                      const int64_t* t, const int64_t* t_prev, const float* acp, float eta,
+                      int clip, int prediction, int64_t B, int64_t per_sample, int dtype,
+                      void* stream) {
   VD_REQUIRE(xt && eps && x_prev && t && t_prev && acp, "null argument");
   VD_REQUIRE(B > 0 && per_sample > 0, "empty tensor");
   VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
+  VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
+             prediction);
   DDIMStep op{acp, t_prev, eta, clip, z != nullptr};
   const bool v8 = per_sample % 8 == 0;
+  const bool pv = prediction == VD_PRED_V;
   const int64_t work = B * per_sample / (v8 ? 8 : 1);
   return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8)
-      ddim_kernel<T, 8><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
+    if (v8 && !pv)
+      ddim_kernel<T, 8, false><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
+          op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
+    else if (!pv)
+      ddim_kernel<T, 1, false><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
+          op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
+    else if (v8)
+      ddim_kernel<T, 8, true><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
           op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
     else
-      ddim_kernel<T, 1><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
+      ddim_kernel<T, 1, true><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
           op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
   });
+}
+
+int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev, void* x0,
+                 const int64_t* t, const int64_t* t_prev, const float* acp, float eta, int clip,
+                 int64_t B, int64_t per_sample, int dtype, void* stream) {
+  return vd_ddim_step_pred(xt, eps, z, x_prev, x0, t, t_prev, acp, eta, clip, VD_PRED_EPS, B,
+                           per_sample, dtype, stream);
 }
 
 size_t vd_cfg_workspace_size(int64_t B, int64_t per_sample) {
@@ -1128,33 +1159,54 @@ int vd_cfg_stats(const void* eps_c, const void* eps_u, float w, int64_t B, int64
   });
 }
 
-int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const void* z,
-                     void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
-                     const int64_t* t_prev, const float* acp, float w, float rescale,
-                     const void* workspace, float eta, int clip, int64_t B, int64_t per_sample,
-                     int dtype, void* stream) {
+int vd_ddim_step_cfg_pred(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                          void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                          const int64_t* t_prev, const float* acp, float w, float rescale,
+                          const void* workspace, float eta, int clip, int prediction,
+                          int64_t B, int64_t per_sample, int dtype, void* stream) {
   VD_REQUIRE(xt && eps_c && eps_u && x_prev && t && t_prev && acp, "null argument");
   VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
              (long long)B, (long long)per_sample);
   VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
   VD_REQUIRE(rescale == 0.f || workspace, "rescale > 0 needs the vd_cfg_stats workspace (null)");
   VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
+  VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
+             prediction);
   DDIMStep op{acp, t_prev, eta, clip, z != nullptr};
   const CfgGuide gd{w};
   const int nb = cfg_blocks(per_sample);
   const float* part = static_cast<const float*>(workspace);
   hipStream_t st = VD_STREAM(stream);
   const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0});
+  const bool pv = prediction == VD_PRED_V;
   return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8)
-      cfg_ddim_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+    if (v8 && !pv)
+      cfg_ddim_kernel<T, 8, false><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
+    else if (!pv)
+      cfg_ddim_kernel<T, 1, false><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
+    else if (v8)
+      cfg_ddim_kernel<T, 8, true><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
           op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
           (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
     else
-      cfg_ddim_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+      cfg_ddim_kernel<T, 1, true><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
           op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
           (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
   });
+}
+
+int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                     void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                     const int64_t* t_prev, const float* acp, float w, float rescale,
+                     const void* workspace, float eta, int clip, int64_t B, int64_t per_sample,
+                     int dtype, void* stream) {
+  return vd_ddim_step_cfg_pred(xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0, t, t_prev, acp, w,
+                               rescale, workspace, eta, clip, VD_PRED_EPS, B, per_sample, dtype,
+                               stream);
 }
 
 int vd_dpm_step(const void* xt, const void* eps, void* x_prev, void* x0_hist, const float* coef,

@@ -16,6 +16,9 @@ LIB_PATH = os.environ.get("VDIFF_LIB") or os.path.join(_HERE, "libvdiff.so")
 VD_F32 = 0
 VD_BF16 = 1
 ABI_VERSION = 1
+# enum vd_prediction / enum vd_loss_weighting
+PREDICTIONS = {"eps": 0, "v": 1}
+LOSS_WEIGHTINGS = {"none": 0, "min-snr": 1}
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -80,6 +83,15 @@ _SIGS = {
                             _vp]),
     "vd_p_sample_cosine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp]),
     "vd_ddim_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i64, _i64, _i, _vp]),
+    "vd_ddim_step_pred": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i64, _i64, _i,
+                               _vp]),
+    "vd_ddim_step_cfg_pred": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp,
+                                   _f, _i, _i, _i64, _i64, _i, _vp]),
+    "vd_diffusion_loss_workspace_size": (_sz, [_i64, _i64]),
+    "vd_diffusion_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _i64, _i64, _i,
+                               _vp, _vp, _vp, _sz, _vp]),
+    "vd_diffusion_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _f, _vp, _i64,
+                                   _i64, _i, _vp, _vp]),
     "vd_cfg_workspace_size": (_sz, [_i64, _i64]),
     "vd_cfg_stats": (_i, [_vp, _vp, _f, _i64, _i64, _i, _vp, _sz, _vp]),
     "vd_ddim_step_cfg": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f,

@@ -74,6 +74,19 @@ def audio_keep_mask(batch, p, device, generator=None):
     return (u >= p).to(torch.float32)
 
 
+def _sqrt_tables(scheduler):
+    """(sqrt_acp, sqrt_1m_acp) of a DDPM scheduler as fp32 CPU vectors: the two tables its
+    q_sample reads, under either family's attribute names."""
+    for names in (("sqrt_alpha_cum_prod", "sqrt_one_minus_alpha_cum_prod"),
+                  ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")):
+        if all(hasattr(scheduler, n) for n in names):
+            return tuple(getattr(scheduler, n).detach().float().cpu().contiguous()
+                         for n in names)
+    raise ValueError(f"{type(scheduler).__name__} has no sqrt_alpha_cum_prod / "
+                     "sqrt_one_minus_alpha_cum_prod tables: a non-default objective and "
+                     "v-prediction sampling read them")
+
+
 class Trainer:
     """q_sample -> denoiser -> MSE(eps_pred, eps) -> backward -> all-reduce -> Adam.
 
@@ -84,8 +97,24 @@ class Trainer:
                  audio_drop_prob=0.0, drop_generator=None, ema_rates=(), ema_warmup=False,
                  clip_grad_norm=None, optimizer="torch", weight_decay=0.0,
                  decoupled_weight_decay=True, lr_warmup=0, lr_schedule="constant",
-                 lr_total_steps=None, lr_min_ratio=0.0, skip_bad_steps=0):
-        """check_every: the loss finiteness flag (kept on the device, updated every step) is
+                 lr_total_steps=None, lr_min_ratio=0.0, skip_bad_steps=0, prediction="eps",
+                 loss_weighting="none", snr_gamma=5.0, objective_fn=None):
+        """prediction, loss_weighting, snr_gamma: the training objective.  The defaults ("eps",
+        "none") are the reference's: the model predicts the noise and the loss is loss_fn(pred,
+        eps), ops.mse_loss, exactly as before.  prediction="v" trains the model on v =
+        sqrt_acp[t] eps - sqrt_1m_acp[t] x0 (Salimans & Ho 2022); loss_weighting="min-snr"
+        weighs each sample by min(snr, snr_gamma) / snr (eps) or / (snr + 1) (v), snr =
+        (sqrt_acp[t] / sqrt_1m_acp[t])^2 (Hang et al. 2023).  Either one replaces the loss by
+        ops.diffusion_loss(pred, x0, eps, t, ...) (vd_diffusion_loss: fixed-order, no host
+        sync, graph-safe) on the scheduler's own q_sample tables, eagerly and inside
+        TrainStepGraph; self.loss_per_sample is then the last step's unweighted per-sample MSE
+        (a [B] device view, rewritten by the next step; None on the default path).  A loss_fn
+        cannot be combined with them (ValueError), and the weighting refuses a schedule with a
+        table entry sqrt_acp == 0 or sqrt_1m_acp == 0 (an infinite or zero snr).
+        objective_fn: (pred, x0, eps, t) -> (loss, per-sample MSE) used in place of
+        ops.diffusion_loss for a non-default objective: host-logic tests on CPU pass a torch
+        restatement (the product op refuses CPU tensors).
+        check_every: the loss finiteness flag (kept on the device, updated every step) is
         read on the host every `check_every` steps and by check_finite(); a non-finite
         loss raises FloatingPointError naming the first bad step.  0 disables it.
         batch_pack: re-pack the conv operands once per step in one launch
@@ -146,6 +175,38 @@ class Trainer:
             from .clip import GradClipper, check_max_norm
             self.clipper = GradClipper(check_max_norm(clip_grad_norm, "clip_grad_norm"))
         self._bad_grad = None  # device bool: the first bad step had a finite loss (bad norm)
+        ops.prediction_id(prediction)
+        ops.weighting_id(loss_weighting)
+        if not (isinstance(snr_gamma, (int, float)) and snr_gamma > 0
+                and math.isfinite(snr_gamma)):
+            raise ValueError(f"snr_gamma {snr_gamma!r} is not a positive finite number")
+        self.prediction, self.loss_weighting = prediction, loss_weighting
+        self.snr_gamma = float(snr_gamma)
+        # None: the default objective, which runs loss_fn(pred, eps) exactly as before
+        self.objective = None
+        self.loss_per_sample = None
+        if (prediction, loss_weighting) != ("eps", "none"):
+            if loss_fn is not None:
+                raise ValueError(f"Trainer(loss_fn=...) is the loss of the default objective "
+                                 f"only; prediction={prediction!r}, loss_weighting="
+                                 f"{loss_weighting!r} compute their own (objective_fn replaces "
+                                 "it in CPU tests)")
+            sa, s1m = _sqrt_tables(scheduler)
+            if loss_weighting != "none":
+                bad = ((sa == 0) | (s1m == 0)).nonzero().flatten()
+                if bad.numel():
+                    i = int(bad[0])
+                    raise ValueError(
+                        f"loss_weighting={loss_weighting!r}: schedule entry {i} of "
+                        f"{sa.numel()} has sqrt_acp = {float(sa[i])!r}, sqrt_1m_acp = "
+                        f"{float(s1m[i])!r} in fp32; the signal-to-noise ratio there is "
+                        "infinite or zero and has no weight")
+            self.objective = (sa, s1m)
+        elif objective_fn is not None:
+            raise ValueError("Trainer(objective_fn=...) stands in for ops.diffusion_loss and "
+                             "needs a non-default prediction or loss_weighting")
+        self.objective_fn = objective_fn
+        self._objective_dev = {}
         self.loss_fn = loss_fn or ops.mse_loss
         self.scheduler = scheduler
         self.check_every = int(check_every)
@@ -225,7 +286,7 @@ class Trainer:
                 pred = self.model(xt, clip.cond, clip.audio, clip.t)
             else:
                 pred = self.model(xt, clip.cond, clip.audio, clip.t, audio_keep=keep)
-            loss = self.loss_fn(pred, clip.eps)
+            loss = self._loss(pred, clip.x0, clip.eps, clip.t)
             loss.backward()
         if self.bucketer is not None:
             self.bucketer.finish()
@@ -240,6 +301,27 @@ class Trainer:
         loss = loss.detach()
         self._track_finite(loss)
         self._update_ema()
+        return loss
+
+    def _loss(self, pred, x0, eps, t):
+        """The step's loss.  Default objective: loss_fn(pred, eps), as before.  Otherwise
+        ops.diffusion_loss (or objective_fn) on the scheduler's q_sample tables, which also
+        leaves the per-sample MSE in self.loss_per_sample."""
+        if self.objective is None:
+            return self.loss_fn(pred, eps)
+        if self.objective_fn is not None:
+            loss, per = self.objective_fn(pred, x0, eps, t)
+        else:
+            key = str(pred.device)
+            if key not in self._objective_dev:
+                self._objective_dev[key] = tuple(
+                    v.to(device=pred.device, dtype=torch.float32).contiguous()
+                    for v in self.objective)
+            sa, s1m = self._objective_dev[key]
+            loss, per = ops.diffusion_loss(pred, x0, eps, t, sa, s1m, self.prediction,
+                                           self.loss_weighting, self.snr_gamma,
+                                           return_per_sample=True)
+        self.loss_per_sample = per.detach()
         return loss
 
     @property
@@ -421,6 +503,7 @@ class TrainStepGraph:
                              (self.cond, clip.cond), (self.feats, enc)):
                 dst.copy_(src)
         self.g.replay()
+        tr.loss_per_sample = self.per  # (an eager step in between left its own there)
         if enc.requires_grad:
             enc.backward(self.feats.grad)
         tr._clip_grads()  # eager, like Adam: the graph's static gradients and the encoder's
@@ -456,7 +539,9 @@ class TrainStepGraph:
         with tr.packs:
             xt = tr.scheduler.add_noise(self.x0, self.eps, self.t)
             pred = tr.model(xt, self.cond, self.feats, self.t)
-            loss = tr.loss_fn(pred, self.eps)
+            # a non-default objective: vd_diffusion_loss on the static x0 / eps / t buffers,
+            # built to the same rules; loss_per_sample then lives in the pool as well
+            loss = tr._loss(pred, self.x0, self.eps, self.t)
             self.loss = loss.detach()  # lives in the graph's pool, rewritten by each replay
             loss.backward()
 
@@ -490,6 +575,7 @@ class TrainStepGraph:
         finally:
             lib.vd_set_dropout_counter(None)
         self.g.instantiate()
+        self.per = tr.loss_per_sample  # None on the default path
         self.shapes = self._shapes(clip, enc)
         tr.packs.frozen = True  # the graph replays the pack launch into these buffers
         self.grads = [(p, p.grad) for p in model.parameters() if p.grad is not None]
@@ -533,7 +619,8 @@ class DDIMGraph:
     ops.frozen_weights() (the graph reads the cached packed conv weights); eta must be 0.
 
     guidance_scale != 1 (classifier-free audio guidance): the captured step is the UNet forward
-    at batch 2B + vd_cfg_stats (guidance_rescale > 0) + vd_ddim_step_cfg.  The graph owns a
+    at batch 2B + vd_cfg_stats (guidance_rescale > 0) + vd_ddim_step_cfg.  The model's output is
+    read as sampler.prediction says ("eps" or "v"; the same launches either way).  The graph owns a
     static [2B, ...] input whose halves are the fused kernel's x_prev and x_prev_dup, so the
     doubled input stays current without a copy; the doubled cond / audio / timestep buffers and
     the null audio are built here, before capture (no memset node in the step)."""
@@ -569,11 +656,13 @@ class DDIMGraph:
             eps_c, eps_u = eps.to(self.xt.dtype).chunk(2)
             _, x0 = ops.ddim_step_cfg(self.xt, eps_c, eps_u, self.t[:B], self.tp[:B], self.acp,
                                       self.scale, self.rescale, clip=self.sampler.clip_x0,
-                                      out=self.xt, dup=self.xdup)
+                                      out=self.xt, dup=self.xdup,
+                                      prediction=self.sampler.prediction)
             return x0
         eps = self.model(self.xt, self.cond, self.feats, self.t)
         xp, x0 = ops.ddim_step(self.xt, eps.to(self.xt.dtype), self.t, self.tp, self.acp,
-                               eta=0.0, clip=self.sampler.clip_x0)
+                               eta=0.0, clip=self.sampler.clip_x0,
+                               prediction=self.sampler.prediction)
         self.xt.copy_(xp.view_as(self.xt))
         return x0
 
@@ -759,17 +848,36 @@ def _sample_dpm(model, sampler, cond, audio, shape, generator, callback, scale=1
 
 @torch.no_grad()
 def sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps=None, generator=None,
-                callback=None, guidance_scale=1.0, guidance_rescale=0.0):
+                callback=None, guidance_scale=1.0, guidance_rescale=0.0, prediction="eps"):
     """Ancestral sampling as test.py:51-83 (V2 scheduler by default there).  guidance_scale !=
     1: classifier-free audio guidance as in sample_ddim; the guided noise (ops.cfg_combine) is
-    the eps of the scheduler's p_sample kernel."""
+    the eps of the scheduler's p_sample kernel.  prediction="v": the model's (guided) output is
+    v, and eps = sqrt_1m_acp[t] xt + sqrt_acp[t] v is formed by one extra launch per step --
+    ops.q_sample(v, xt, t, ...) on the scheduler's own tables -- before the unchanged p_sample
+    kernel."""
+    ops.prediction_id(prediction)
     with ops.frozen_weights():
         return _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator,
-                            callback, float(guidance_scale), float(guidance_rescale))
+                            callback, float(guidance_scale), float(guidance_rescale), prediction)
+
+
+def v_to_eps(scheduler, v, xt, t):
+    """eps = sqrt_1m_acp[t] xt + sqrt_acp[t] v of a v-prediction model's output, in xt's dtype:
+    vd_q_sample with v in x0's place and xt in the noise's."""
+    sa, s1m = _v_tables(scheduler, xt.device)
+    return ops.q_sample(v.contiguous().to(xt.dtype), xt.contiguous(), t, sa, s1m)
+
+
+def _v_tables(scheduler, device):
+    cache = scheduler.__dict__.setdefault("_v_tables_dev", {})
+    key = str(device)
+    if key not in cache:
+        cache[key] = tuple(v.to(device) for v in _sqrt_tables(scheduler))
+    return cache[key]
 
 
 def _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator, callback,
-                 scale=1.0, rescale=0.0):
+                 scale=1.0, rescale=0.0, prediction="eps"):
     model.eval()
     device = cond.device
     feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
@@ -785,6 +893,8 @@ def _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator, c
             eps = ops.cfg_combine(eps_c, eps_u, scale, rescale)
         else:
             eps = model(xt, cond, feats, t)
+        if prediction == "v":
+            eps = v_to_eps(scheduler, eps, xt, t)
         z = torch.randn(xt.shape, generator=generator, device=device)
         xt, x0 = scheduler.sample_prev_timestep(xt, eps, t, z=z)
         if callback is not None:

@@ -8,6 +8,7 @@ injected (tests) or is drawn with torch.randn_like on the tensor's device.
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -104,9 +105,15 @@ class DDIMSampler:
     (build extension: the reference samples with 500-step DDPM V2, test.py:111).
 
     steps: number of denoising steps; timesteps = linspace(T-1, 0, steps) rounded.
+    prediction: what the denoiser's output is, "eps" (the default) or "v" (v = sqrt(a_t) eps -
+    sqrt(1 - a_t) x0, Salimans & Ho 2022): the step kernel then forms x0 = sqrt(a_t) xt -
+    sqrt(1 - a_t) v and eps = sqrt(1 - a_t) xt + sqrt(a_t) v itself.  step() and step_guided()
+    take the model's output under the name noise_pred / eps_c, eps_u either way.
     """
 
-    def __init__(self, scheduler, steps=50, eta=0.0, clip_x0=False):
+    def __init__(self, scheduler, steps=50, eta=0.0, clip_x0=False, prediction="eps"):
+        ops.prediction_id(prediction)  # ValueError on anything but "eps" / "v"
+        self.prediction = prediction
         acp = getattr(scheduler, "alpha_cum_prod", None)
         if acp is None:
             acp = scheduler.alphas_cumprod
@@ -134,7 +141,8 @@ class DDIMSampler:
         if self.eta > 0 and z is None:
             z = torch.randn_like(xt)
         return ops.ddim_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), t, tp,
-                             self._acp(xt.device), eta=self.eta, z=z, clip=self.clip_x0)
+                             self._acp(xt.device), eta=self.eta, z=z, clip=self.clip_x0,
+                             prediction=self.prediction)
 
     def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, z=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
@@ -146,7 +154,21 @@ class DDIMSampler:
             z = torch.randn_like(xt)
         return ops.ddim_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
                                  eps_u.contiguous().to(xt.dtype), t, tp, self._acp(xt.device),
-                                 scale, rescale, eta=self.eta, z=z, clip=self.clip_x0)
+                                 scale, rescale, eta=self.eta, z=z, clip=self.clip_x0,
+                                 prediction=self.prediction)
+
+
+def _prediction_keyword(init):
+    """Gives a sampler's initialiser the keyword-only option prediction="eps" | "v": checked
+    and stored as self.prediction before the initialiser runs.  The positional parameters, which
+    callers and the 2M tests rely on, stay exactly the initialiser's own (functools.wraps: that
+    is also the signature introspection reports)."""
+    @functools.wraps(init)
+    def with_prediction(self, *args, prediction="eps", **kw):
+        ops.prediction_id(prediction)  # ValueError on anything but "eps" / "v"
+        self.prediction = prediction
+        init(self, *args, **kw)
+    return with_prediction
 
 
 class DPMSolverSampler:
@@ -154,9 +176,9 @@ class DPMSolverSampler:
     subsequence of a DDPM schedule's acp table.  It reuses the previous step's x0 prediction
     instead of a second forward, so a step costs what a DDIM step costs.  This is diffusers'
     DPMSolverMultistepScheduler with algorithm_type="dpmsolver++", solver_type="midpoint",
-    lower_order_final=True and a zero final sigma; noise (epsilon) prediction only.  Not here:
-    the stochastic (SDE) variants, third-order and singlestep solvers, dynamic thresholding and
-    v-prediction.
+    lower_order_final=True and a zero final sigma, for prediction_type "epsilon" (the default)
+    or "v_prediction" (prediction="v").  Not here: the stochastic (SDE) variants, third-order
+    and singlestep solvers, dynamic thresholding and x0-prediction.
 
     With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h = lambda_prev -
     lambda_t and k = -alpha_prev expm1(-h), a step is
@@ -170,6 +192,14 @@ class DPMSolverSampler:
     self.coef64 holds the rows [alpha_t, sigma_t, A, B, C, 0, 0, 0] in fp64, self.coef the same
     rounded once to fp32: the table the kernel reads.
 
+    prediction="v" (the denoiser predicts v = alpha_t eps - sigma_t x0, Salimans & Ho 2022)
+    needs no other kernel: x0 = alpha_t xt - sigma_t v = (xt - (sigma_t / alpha_t) v) / (1 /
+    alpha_t), so columns 0 and 1 of the rows hold 1 / alpha_t and sigma_t / alpha_t instead
+    (coef64 in fp64, coef rounded once from it) and vd_dpm_step / vd_dpm_step_cfg do the rest
+    on the model's v, guided or not, eager or replayed; A, B and C do not depend on the
+    parameterisation and keep their bits.  The guide and the std-rescale then act on v, as Lin
+    et al. 2023 define the rescale.
+
     spacing: "logsnr" (default) picks the timesteps nearest to `steps` values of lambda spread
     uniformly from lambda[T-1] to lambda[0] (lowest index on a tie, duplicates dropped, so
     self.steps may be smaller than asked for); "linspace" is DDIMSampler's rule.  On linspace
@@ -179,7 +209,9 @@ class DPMSolverSampler:
     The sampler keeps no history: step() takes the previous step's x0 and returns this one's.
     """
 
+    @_prediction_keyword
     def __init__(self, scheduler, steps=20, order=2, spacing="logsnr", clip_x0=False):
+        prediction = self.prediction  # keyword-only, validated and stored by the decorator
         acp = getattr(scheduler, "alpha_cum_prod", None)
         if acp is None:
             acp = scheduler.alphas_cumprod
@@ -225,6 +257,10 @@ class DPMSolverSampler:
             else:
                 coef[i, 3] = k
         coef[n - 1, 3] = 1.0
+        if prediction == "v":
+            # the kernel's (xt - c1 out) / c0 with c0 = 1 / alpha, c1 = sigma / alpha is
+            # alpha xt - sigma v: the x0 of a v-prediction model (class docstring)
+            coef[:, 0], coef[:, 1] = 1.0 / alpha, sigma / alpha
         self.coef64 = coef
         self.coef = coef.float()
         self._dev = {}

@@ -2,7 +2,7 @@
 
     python test.py [--ckpt model.pth | --random-init] [--sampler ddpm-v2|ddim|dpm++]
                    [--steps 500] [--spacing logsnr|linspace]
-                   [--guidance-scale 1.0] [--guidance-rescale 0.0]
+                   [--guidance-scale 1.0] [--guidance-rescale 0.0] [--prediction eps|v]
 
 Reference API kept (importable without running anything, unlike the reference script):
   * `config` -- the dict of test.py:33-49 (same keys; `ldm_params` may also carry the
@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 import _vdiff_path  # noqa: F401
-from vdiff.engine import reinit_nonzero, sample_ddim, sample_dpm, synthetic_clip
+from vdiff.engine import reinit_nonzero, sample_ddim, sample_dpm, synthetic_clip, v_to_eps
 from vdiff.ops import cfg_combine, frozen_weights
 
 from linear_noise_scheduler import LinearNoiseSchedulerV2
@@ -118,7 +118,7 @@ def _frames_of(model, audio_cond):
 @torch.no_grad()
 def sample_images(model, scheduler, img_cond, audio_cond, n_timesteps=500, *, out_dir=OUT_DIR,
                   save_every=50, generator=None, noise=None, max_steps=None, callback=None,
-                  guidance_scale=1.0, guidance_rescale=0.0):
+                  guidance_scale=1.0, guidance_rescale=0.0, prediction="eps"):
     """test.py:51-83: reverse process i = n_timesteps-1 .. 0 with
     scheduler.sample_prev_timestep (LinearNoiseSchedulerV2 in test.py), x0 saved every
     `save_every` steps and at i == 0; returns the final x0.
@@ -128,7 +128,10 @@ def sample_images(model, scheduler, img_cond, audio_cond, n_timesteps=500, *, ou
     many steps; `callback(i, xt, x0)` sees every step's output; `guidance_scale` != 1 samples
     with classifier-free audio guidance (one forward at batch 2, the second row with the null
     audio; `guidance_rescale` is the std-rescale of Lin et al. 2023), for a model trained with
-    train.py --audio-drop-prob."""
+    train.py --audio-drop-prob; `prediction` = "v" for a model trained with train.py
+    --prediction v (its output, guided or not, is turned into the noise by one extra launch)."""
+    if prediction not in ("eps", "v"):
+        raise ValueError(f"prediction {prediction!r}: 'eps' or 'v'")
     model.eval()
     dev = img_cond.device
     S = config["dataset_params"]["im_size"]
@@ -154,6 +157,8 @@ def sample_images(model, scheduler, img_cond, audio_cond, n_timesteps=500, *, ou
                 eps = cfg_combine(eps_c, eps_u, guidance_scale, guidance_rescale)
             else:
                 eps = model(xt, img_cond, feats, t)
+            if prediction == "v":
+                eps = v_to_eps(scheduler, eps, xt, t)
             z = draw(xt.shape).to(dev)
             xt, x0 = scheduler.sample_prev_timestep(xt, eps, t, z=z)
             if callback is not None:
@@ -191,6 +196,9 @@ def parse(argv=None):
                          "with --audio-drop-prob)")
     ap.add_argument("--guidance-rescale", type=float, default=0.0,
                     help="std-rescale of the guided noise in [0, 1] (Lin et al. 2023)")
+    ap.add_argument("--prediction", default="eps", choices=["eps", "v"],
+                    help="what the checkpoint's denoiser predicts (train.py --prediction); every "
+                         "sampler reads its output accordingly")
     args = ap.parse_args(argv)
     if args.steps is None and args.sampler == "dpm++":
         args.steps = 20
@@ -229,9 +237,11 @@ def main(argv=None):
         shape = (1, 3, frames, args.image_size, args.image_size) if args.dims == 3 else \
             (1, 3, args.image_size, args.image_size)
         if args.sampler == "ddim":
-            sampler, sample = DDIMSampler(scheduler, steps=args.steps or 50), sample_ddim
+            sampler = DDIMSampler(scheduler, steps=args.steps or 50, prediction=args.prediction)
+            sample = sample_ddim
         else:
-            sampler = DPMSolverSampler(scheduler, steps=args.steps or 20, spacing=args.spacing)
+            sampler = DPMSolverSampler(scheduler, steps=args.steps or 20, spacing=args.spacing,
+                                       prediction=args.prediction)
             sample = sample_dpm
 
         def cb(i, xt, x0):
@@ -246,7 +256,7 @@ def main(argv=None):
     return sample_images(model, scheduler, cond, audio, n_timesteps=args.steps or 500,
                          out_dir=args.out_dir, save_every=args.save_every, generator=g,
                          guidance_scale=args.guidance_scale,
-                         guidance_rescale=args.guidance_rescale)
+                         guidance_rescale=args.guidance_rescale, prediction=args.prediction)
 
 
 if __name__ == "__main__":
