@@ -146,3 +146,211 @@ def test_attention_reference_and_row_statistic(mode, B, C, T, HW):
                                                                  cat(ref, ref["dq"]))
     assert moved < 1e-2
     assert A.row_stat(bad, ref["dq"]) > 4 * A.row_stat(emu["dq"], ref["dq"])
+
+
+# ------------------------------------------- multi-head and cross-attention per-row checks
+@pytest.mark.parametrize("legacy", [True, False])
+@pytest.mark.parametrize("mode,B,C,heads,T,HW", [("joint", 2, 64, 2, 3, 23),
+                                                 ("spatial", 2, 64, 4, 5, 13),
+                                                 ("temporal", 1, 64, 2, 9, 7)])
+def test_attention_sequences_split_heads_like_the_oracle(mode, B, C, heads, T, HW, legacy):
+    """tests/_attn_rows.py sequences(heads, legacy): the fp64 reference on the split sequences
+    equals oracle.nn.qkv_attention(heads, legacy) and its autograd in all three groupings, to the
+    oracle's fp32 softmax."""
+    from oracle import nn as onn
+    import _attn_rows as A
+    N = T * HW
+    qkv = seeded((B, 3 * C, N), 7).bfloat16().float()
+    g = seeded((B, C, N), 8).bfloat16().float()
+    qr = qkv.double().requires_grad_(True)
+    out = onn.qkv_attention(qr, heads, legacy=legacy, mode=mode, spatial=(T, HW, 1))
+    out.backward(g.double())
+    q, k, v = A.sequences(qkv, C, T, HW, mode, heads, legacy)
+    do, = A.sequences(g, C, T, HW, mode, heads, legacy)
+    assert q.shape[-1] == C // heads
+    ref, _, _ = A.reference(q, k, v, do, False)
+    want = dict(zip(("dq", "dk", "dv"), A.sequences(qr.grad, C, T, HW, mode, heads, legacy)))
+    want["o"], = A.sequences(out.detach(), C, T, HW, mode, heads, legacy)
+    for name in ref:
+        assert float((ref[name] - want[name]).abs().max()) < 2e-6, name
+
+
+@pytest.mark.parametrize("heads", [1, 2, 4])
+@pytest.mark.parametrize("per_frame", [True, False])
+def test_cross_attention_reference_matches_the_oracle(per_frame, heads):
+    """The cross reference (cross_q_sequences / cross_kv_sequences + reference), per frame and at
+    clip level, equals oracle.nn.cross_attention and its autograd to the oracle's fp32 softmax."""
+    from oracle import nn as onn
+    import _attn_rows as A
+    B, C, T, HW, L = 2, 64, 3, 13, 5
+    q = seeded((B, C, T * HW), 9).bfloat16().float()
+    kv = seeded((B * T, L, 2 * C), 10).bfloat16().float()
+    g = seeded((B, C, T * HW), 11).bfloat16().float()
+    qr, kvr = q.double().requires_grad_(True), kv.double().requires_grad_(True)
+    out = onn.cross_attention(qr, kvr, heads, T, per_frame)
+    out.backward(g.double())
+    k, v = A.cross_kv_sequences(kv, heads, T, per_frame)
+    ref, lse, _ = A.reference(A.cross_q_sequences(q, heads, T, per_frame), k, v,
+                              A.cross_q_sequences(g, heads, T, per_frame), False)
+    assert ref["o"].shape == ((B * T if per_frame else B) * heads, HW if per_frame else T * HW,
+                              C // heads)
+    assert k.shape[1] == (L if per_frame else T * L)
+    want = dict(o=A.cross_q_sequences(out.detach(), heads, T, per_frame),
+                dq=A.cross_q_sequences(qr.grad, heads, T, per_frame))
+    want["dk"], want["dv"] = A.cross_kv_sequences(kvr.grad, heads, T, per_frame)
+    for name in ref:
+        assert float((ref[name] - want[name]).abs().max()) < 2e-6, name
+
+
+def _self_case_params():
+    import _attn_rows as A
+    return [pytest.param(c, legacy, id=A.case_id(c[:8]) + f"-legacy{int(legacy)}")
+            for c in A.SELF_CASES if c[8] == "auto"
+            for legacy in ((True, False) if c[2] > 1 else (True,))]
+
+
+@pytest.mark.parametrize("case,legacy", _self_case_params())
+def test_attention_gpu_self_cases_keep_the_emulation_cap(case, legacy):
+    """Every multi-head / amp self-attention GPU case: the emulation's own statistic <= 1.5e-2
+    for every output and its lse error <= 1.0 of the bound (measured 4.0e-3 - 8.7e-3, lse at most
+    0.28; amp = 1.5: 1.37e-2 and 0.24)."""
+    import _attn_rows as A
+    B, C, heads, T, HW, mode, seed, amp, _ = case
+    _, _, host = A.self_inputs(B, C, T, HW, mode, seed, amp, heads, legacy)
+    print(case, legacy, host.emu_stat)
+    host.assert_cap()
+
+
+def _cross_case_params():
+    import _attn_rows as A
+    return [pytest.param(c, id=A.case_id(c)) for c in A.CROSS_CASES]
+
+
+@pytest.mark.parametrize("case", _cross_case_params())
+def test_attention_gpu_cross_cases_keep_the_emulation_cap(case):
+    """Every cross-attention GPU case: the same cap (measured 3.1e-3 - 8.6e-3, lse at most 0.48;
+    amp = 1.5: 1.21e-2 and 0.54)."""
+    import _attn_rows as A
+    _, _, _, host = A.cross_inputs(*case)
+    print(case, host.emu_stat)
+    host.assert_cap()
+
+
+def test_cross_mutations_pass_the_whole_tensor_bar_and_fail_per_row():
+    """At (nseq, Lq, Lk, C) = (1, 3000, 12, 64), the query-split case: (a) dK row 5 summed
+    without queries 2944..2999, the last, partial query tile, moves the whole-tensor rel-L2 of
+    d(kv) to 0.025 (bar 4e-2) and the row statistic to 0.125, against 4 x 4.3e-3; (b) one dQ row
+    of 3000 scaled by 0.9 leaves the rel-L2 of dq at 5e-3 and the row statistic at 0.099, against
+    4 x 7.5e-3."""
+    import _attn_rows as A
+    _, _, _, h = A.cross_inputs(1, 64, 1, 1, 3000, 12, True, 410)
+    bad = h.emu["dk"].clone()
+    part, _, _ = A.reference(h.q[:, :2944], h.k, h.v, h.do[:, :2944], True)
+    # the softmax is per query row, so dK over a subset of the queries is the reference on them
+    bad[0, 5] = part["dk"][0, 5]
+    cat = lambda dk, dv: torch.cat([dk, dv], -1)  # noqa: E731
+    whole = rel_l2(cat(bad, h.emu["dv"]), cat(h.ref["dk"], h.ref["dv"]))
+    row = A.row_stat(bad, h.ref["dk"])
+    print("dK without the last query tile:", whole, row, h.emu_stat["dk"])
+    assert whole < 4e-2
+    assert row > 4 * h.emu_stat["dk"]
+    bad = h.emu["dq"].clone()
+    bad[0, 1234] *= 0.9
+    whole = rel_l2(bad, h.ref["dq"])
+    row = A.row_stat(bad, h.ref["dq"])
+    print("one dQ row x 0.9:", whole, row, h.emu_stat["dq"])
+    assert whole < 4e-2
+    assert row > 4 * h.emu_stat["dq"]
+
+
+def test_cross_wrong_audio_window_exceeds_the_row_limit_on_o():
+    """The last frame of a batch element attending to the previous frame's audio window (an
+    off-by-one in the frame -> window mapping): O of that frame's rows is far outside 4 x the
+    emulation's statistic (measured 2.1 against 4 x 4.0e-3)."""
+    import _attn_rows as A
+    B, C, heads, T, HW, L = 2, 64, 1, 3, 67, 12
+    _, _, _, h = A.cross_inputs(B, C, heads, T, HW, L, True, 464)
+    seq = (0 * T + T - 1) * heads      # sequence (b = 0, t = T - 1, h = 0)
+    wrong, _, _ = A.reference(h.q[seq:seq + 1], h.k[seq - heads:seq - heads + 1],
+                              h.v[seq - heads:seq - heads + 1], h.do[seq:seq + 1], True)
+    bad = h.emu["o"].clone()
+    bad[seq] = wrong["o"][0]
+    row = A.row_stat(bad, h.ref["o"])
+    print("wrong audio window:", row, h.emu_stat["o"])
+    assert row > 4 * h.emu_stat["o"]
+    assert A.row_stat(h.emu["o"], h.ref["o"]) <= 4 * h.emu_stat["o"]
+
+
+# ------------------------------------------- LayerNorm (tests/test_gpu_layernorm_bounds.py)
+def _ln_torch(x, dy, w, b, dt, bf=False):
+    """torch's own layer_norm and its autograd in dt; y and dx rounded to bf16 in bf16 mode."""
+    from test_gpu_layernorm_bounds import EPS
+    xr, wr, br = (t.detach().to(dt).clone().requires_grad_(True) for t in (x, w, b))
+    y = F.layer_norm(xr, (x.shape[1],), wr, br, EPS)
+    y.backward(dy.to(dt))
+    r = bf16r if bf else (lambda t: t)
+    return r(y.detach()), r(xr.grad), wr.grad, br.grad
+
+
+def test_layernorm_reference_matches_autograd():
+    """ln_ref in fp64 against F.layer_norm and its autograd; every magnitude bounds its value."""
+    from test_gpu_layernorm_bounds import ln_inputs, ln_ref
+    for case in ((37, 256, "randn"), (67, 1544, "offset"), (9, 520, "const")):
+        x, dy, w, b = ln_inputs(case, True)
+        ref, mag, (mu, rstd, mabs, var) = ln_ref(x, dy, w, b, torch.float64)
+        for a, t, m in zip(ref, _ln_torch(x, dy, w, b, torch.float64), mag):
+            assert float((a - t).abs().max()) < 1e-11, case
+            assert bool((m >= a.abs() * (1 - 1e-12)).all())
+        assert bool((mabs >= mu.abs()).all())
+
+
+def _ln_case_params():
+    from test_gpu_layernorm_bounds import CASES, case_id
+    return [pytest.param(c, id=case_id(c)) for c in CASES]
+
+
+@pytest.mark.parametrize("bf", [True, False])
+@pytest.mark.parametrize("case", _ln_case_params())
+def test_layernorm_torch_fp32_is_inside_the_bound(case, bf):
+    """torch's fp32 F.layer_norm and its autograd on the CPU, y and dx rounded to bf16 in bf16
+    mode, lie inside the element-wise bound at every GPU case (the constant / zero row case
+    included, which is what keeps it among the GPU cases): the reference alone passes.  Measured
+    largest error / bound: bf16 y 0.97, dx 0.94 (the final rounding); fp32 <= 0.06."""
+    from test_gpu_layernorm_bounds import ln_inputs, ln_judge
+    x, dy, w, b = ln_inputs(case, bf)
+    out = ln_judge(_ln_torch(x, dy, w, b, torch.float32, bf), x, dy, w, b, bf, what=str(case))
+    print(case, bf, out)
+    assert all(v <= 1.0 for k, v in out.items() if not k.startswith("c_"))
+
+
+@pytest.mark.parametrize("bf", [True, False])
+def test_layernorm_mutations_violate_the_bound(bf):
+    """(a) dw without the last row's contribution at (65, 520), the row that is alone in the
+    last backward block: at least 90 % of the columns are outside the bound; (b) one 8-vector of
+    y normalised with the neighbouring row's mean: violations, all inside that vector; both with
+    every other output still inside."""
+    from test_gpu_layernorm_bounds import ln_inputs, ln_judge, ln_ref
+    from _bounds import violations
+    case = (65, 520, "randn")
+    rows, C, _ = case
+    x, dy, w, b = ln_inputs(case, bf)
+    ref, mag, (mu, rstd, _, _) = ln_ref(x, dy, w, b, torch.float64)
+    y, dx, dw, db = _ln_torch(x, dy, w, b, torch.float32, bf)
+    ln_judge((y, dx, dw, db), x, dy, w, b, bf)
+    xh_last = (x[-1].double() - mu[-1]) * rstd[-1]
+    bad_dw = (dw.double() - dy[-1].double() * xh_last).float()
+    n_bad = int(violations(bad_dw, ref[2], mag[2], rows + C, False, 1e-4).sum())
+    print("dw without the last row:", n_bad, "of", C)
+    assert n_bad >= 0.9 * C
+    with pytest.raises(AssertionError, match="outside the bound"):
+        ln_judge((y, dx, bad_dw, db), x, dy, w, b, bf)
+    r, c0 = 40, 512                     # the one 8-vector of chunk 1
+    bad_y = y.clone()
+    rnd = bf16r if bf else (lambda t: t)
+    bad_y[r, c0:c0 + 8] = rnd(((x[r, c0:c0 + 8].double() - mu[r + 1]) * rstd[r] * w[c0:].double()
+                               + b[c0:].double()).float())
+    v = violations(bad_y, ref[0], mag[0], C, bf, 1e-4)
+    print("8-vector with the neighbour's mean:", int(v.sum()), "of 8")
+    assert int(v.sum()) >= 1 and int(v.sum()) == int(v[r, c0:c0 + 8].sum())
+    with pytest.raises(AssertionError, match="outside the bound"):
+        ln_judge((bad_y, dx, dw, db), x, dy, w, b, bf)

@@ -178,3 +178,26 @@ def test_bf16_rows_and_lse_groupings(mode, T, HW):
     dV 7.1e-3 and 6.6e-3 (equal to the emulation); lse 0.13 and 0.23 of the bound."""
     from _attn_rows import check
     check(2, 64, T, HW, mode, 95, record_metric)
+
+
+def _self_cases():
+    from _attn_rows import SELF_CASES, case_id
+    return [pytest.param(c, legacy, id=case_id(c) + f"-legacy{int(legacy)}")
+            for c in SELF_CASES for legacy in ((True, False) if c[2] > 1 else (True,))]
+
+
+@pytest.mark.parametrize("case,legacy", _self_cases())
+def test_bf16_rows_and_lse_heads_and_amp(case, legacy):
+    """The per-row check of test_bf16_rows_and_lse on the bf16 kernels with several heads, in
+    both qkv channel orders (test_multi_head_orders is fp32 only): joint under "auto" and "base",
+    spatial, and temporal with T = 40 > 32 (the flash kernels, one launch per head); and single
+    head with amp = 1.5, a moderately peaked softmax.  Cases (B, C, heads, T, HW, mode, seed,
+    amp, config).  Measured on an MI355X, kernel / emulation: O 4.4e-3 - 1.0e-2 / 4.0e-3 - 9.6e-3
+    (at most 1.27 x, joint with 2 heads), dQ 6.0e-3 - 1.11e-2 (at most 1.05 x), dK 5.9e-3 - 1.37e-2
+    (at most 1.10 x), dV 5.3e-3 - 1.26e-2 (equal to the emulation); lse error 0.11 - 0.28 of its
+    bound, the emulation's the same; "base" and "auto" agree to three digits."""
+    from _attn_rows import check
+    from vdiff import ops
+    B, C, heads, T, HW, mode, seed, amp, cfg = case
+    with ops.attention_config(cfg):
+        check(B, C, T, HW, mode, seed, record_metric, amp, heads, legacy)
