@@ -228,6 +228,38 @@ int vd_dpm_step_cfg(const void* xt, const void* eps_c, const void* eps_u, void* 
                     const int64_t* step, float w, float rescale, const void* workspace,
                     int clip, int64_t B, int64_t per_sample, int dtype, void* stream);
 
+/* Long-clip sampling (build extension, no reference counterpart): a latent of L frames is
+ * denoised as W overlapping windows of T frames, one batched forward per step, and the windows'
+ * predictions are blended back where they overlap (vdiff.engine.sample_long; the tables come
+ * from vdiff.schedulers.WindowPlan).  Contiguous NCTHW, fp32 or bf16 (dtype); HW = H * W.
+ * vd_window_gather: for x [B][C][L][HW],
+ *   win[b * W + w][c][f][hw] = x[b][c][starts[w] + f][hw];
+ * win_dup (may be NULL) receives the same values: the null-audio half of a guided forward, as
+ * x_prev_dup elsewhere.  starts: DEVICE int32 [W]; an entry is clamped into [0, L - T].
+ * vd_window_blend: for win [B * W][C][T][HW],
+ *   out[b][c][l][hw] = sum_k cover_wgt[l][k] * win[b * W + w_k][c][l - starts[w_k]][hw],
+ *   w_k = cover_win[l][k].
+ * cover_win: DEVICE int32 [L][kmax], the windows that cover frame l in ascending order, -1 in
+ * the unused slots; cover_wgt: DEVICE fp32 [L][kmax]; kmax <= VD_WINDOW_KMAX.  The first
+ * product initialises the accumulator, the rest are one fp32 fma each in ascending k, and the
+ * sum is rounded once to dtype.  An entry whose window is outside [0, W) or whose local frame
+ * is outside [0, T) is skipped, so no table content reads out of bounds; a frame without a
+ * valid entry is written as 0.
+ * Both are gathers over output elements -- one element, or one 16-byte vector when HW *
+ * sizeof(element) and every pointer are multiples of 16, per thread over a flat grid: no
+ * atomics, no memset, no workspace, no cross-block communication, so eager and replayed runs
+ * give the same bits.  Null pointers (win_dup excepted), non-positive sizes, T > L, a kmax
+ * outside [1, VD_WINDOW_KMAX] and B * W * C or L * HW of 2^31 or more fail with VD_EINVAL
+ * before any launch. */
+#define VD_WINDOW_KMAX 8
+int vd_window_gather(const void* x, void* win, void* win_dup, const int32_t* starts,
+                     int64_t B, int64_t C, int64_t L, int64_t T, int64_t W, int64_t HW,
+                     int dtype, void* stream);
+int vd_window_blend(const void* win, void* out, const int32_t* starts,
+                    const int32_t* cover_win, const float* cover_wgt, int kmax, int64_t B,
+                    int64_t C, int64_t L, int64_t T, int64_t W, int64_t HW, int dtype,
+                    void* stream);
+
 /* ---- GroupNorm (+SiLU) -------------------------------------------------
  * replaces GroupNorm32 (utils.py:54-56, fp32 statistics) followed by nn.SiLU
  * (unet.py:194-198, 218-225, 297, 624-628).  x, y: [B][S][C] channels-last,

@@ -19,6 +19,7 @@ ABI_VERSION = 1
 # enum vd_prediction / enum vd_loss_weighting
 PREDICTIONS = {"eps": 0, "v": 1}
 LOSS_WEIGHTINGS = {"none": 0, "min-snr": 1}
+WINDOW_KMAX = 8  # VD_WINDOW_KMAX
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -100,6 +101,9 @@ _SIGS = {
     "vd_dpm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _vp]),
     "vd_dpm_step_cfg": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i, _i64,
                              _i64, _i, _vp]),
+    "vd_window_gather": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
+    "vd_window_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i,
+                             _vp]),
     "vd_set_dropout_counter": (None, [_vp]),
     "vd_groupnorm_set_unroll": (_i, [_i]),
     "vd_groupnorm_workspace_size": (_sz, [_i, _i64, _i, _i]),

@@ -846,6 +846,207 @@ def _sample_dpm(model, sampler, cond, audio, shape, generator, callback, scale=1
     return xt, x0
 
 
+class WindowedDenoiser:
+    """The denoiser applied to a long latent through the overlapping windows of a
+    schedulers.WindowPlan: gather the windows (vd_window_gather), run the model on them as one
+    batch (or in chunks of at most `window_batch` windows), blend the predictions back into the
+    long clip (vd_window_blend).  Everything a step needs is built here, before the loop and
+    before any capture: the per-frame audio features routed to the windows by plan.frame_index,
+    cond repeated per window, the null audio of a guided run (zeros) and the static window
+    buffer.  Guided, the window batch is [B * W with the audio; B * W with the null audio], the
+    second half filled by the gather's `dup`, and the blend runs over 2B clips: chunk(2) of the
+    result is (eps_c, eps_u) on the long clip."""
+
+    def __init__(self, model, plan, cond, feats, xt, guided=False, window_batch=None):
+        B, C, L = xt.shape[:3]
+        W, T = plan.num_windows, plan.window
+        if L != plan.length:
+            raise ValueError(f"sample_long: {L} frames for a plan of {plan.length}")
+        if cond.shape[0] != B or feats.shape[0] != B * L:
+            raise ValueError(f"sample_long: cond {tuple(cond.shape)} / encoded audio "
+                             f"{tuple(feats.shape)} do not fit {B} clips of {L} frames (one "
+                             "reference image per clip, one audio window per frame)")
+        if window_batch is not None and int(window_batch) < 1:
+            raise ValueError(f"sample_long: window_batch {window_batch} < 1")
+        dev = xt.device
+        rows = (torch.arange(B, device=dev).view(B, 1) * L
+                + plan.frame_index.to(dev).view(1, W * T)).reshape(-1)
+        feats = feats.index_select(0, rows)              # [B * W * T, ...]
+        cond = cond.repeat_interleave(W, dim=0)          # [B * W, ...]
+        if guided:
+            cond, feats = _doubled(cond, feats)
+        self.model, self.plan, self.guided = model, plan, guided
+        self.cond, self.feats = cond, feats
+        self.half = B * W
+        self.rows = (2 if guided else 1) * B * W         # of the window batch and its timesteps
+        self.chunk = self.rows if window_batch is None else min(int(window_batch), self.rows)
+        self.win = torch.empty((self.rows, C, T) + tuple(xt.shape[3:]), dtype=xt.dtype,
+                               device=dev)
+
+    def __call__(self, xt, t):
+        """The model's output on the long clip: [B, ...] like xt, or [2B, ...] guided.  t: the
+        window batch's timesteps, [self.rows]."""
+        n, T = self.half, self.plan.window
+        ops.window_gather(xt, self.plan, out=self.win[:n],
+                          dup=self.win[n:] if self.guided else None)
+        outs = []
+        for i in range(0, self.rows, self.chunk):
+            j = min(i + self.chunk, self.rows)
+            outs.append(self.model(self.win[i:j], self.cond[i:j], self.feats[i * T:j * T],
+                                   t[i:j]))
+        eps = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return ops.window_blend(eps.to(xt.dtype).contiguous(), self.plan)
+
+
+class _LongGraph:
+    """Buffer setup of the long-clip graphs: the long latent and its history are static, the
+    model input is WindowedDenoiser's window buffer, and the timestep buffers have one row per
+    window of the batch (B * W, or 2 B * W guided) -- the step kernels read the first B."""
+
+    def _setup(self, model, sampler, windows, xt, guidance_scale, guidance_rescale):
+        self.model, self.sampler, self.windows = model, sampler, windows
+        self.scale, self.rescale = float(guidance_scale), float(guidance_rescale)
+        self.guided = windows.guided
+        self.xt = xt.clone()
+        # the buffer capture() saves and restores around its warm-up: the long latent itself
+        # (the window buffer is rewritten from it by every step's gather)
+        self.x2 = self.xt
+        self.cond, self.feats = windows.cond, windows.feats
+        self.t_all = sampler.timesteps.to(xt.device).view(-1, 1).expand(-1, windows.rows) \
+            .contiguous()
+        self.t = self.t_all[0].clone()
+        self.graph = None
+
+
+class LongDDIMGraph(_LongGraph, DDIMGraph):
+    """DDIMGraph for a long clip: the captured step is gather + the UNet forward at batch B * W
+    (2 B * W guided) + blend + the same vd_ddim_step / vd_cfg_stats + vd_ddim_step_cfg launches
+    on the long tensors."""
+
+    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0):
+        if sampler.eta != 0:
+            raise ValueError("LongDDIMGraph: eta = 0 (deterministic DDIM) only")
+        self._setup(model, sampler, windows, xt, guidance_scale, guidance_rescale)
+        self.tp_all = sampler.prev_timesteps.to(xt.device).view(-1, 1) \
+            .expand(-1, windows.rows).contiguous()
+        self.tp = self.tp_all[0].clone()
+        self.acp = sampler._acp(xt.device)
+        self.x0 = None
+
+    def _body(self):
+        B = self.xt.shape[0]
+        eps = self.windows(self.xt, self.t)
+        if self.guided:
+            eps_c, eps_u = eps.chunk(2)
+            _, x0 = ops.ddim_step_cfg(self.xt, eps_c, eps_u, self.t[:B], self.tp[:B], self.acp,
+                                      self.scale, self.rescale, clip=self.sampler.clip_x0,
+                                      out=self.xt, prediction=self.sampler.prediction)
+            return x0
+        xp, x0 = ops.ddim_step(self.xt, eps, self.t[:B], self.tp[:B], self.acp, eta=0.0,
+                               clip=self.sampler.clip_x0, prediction=self.sampler.prediction)
+        self.xt.copy_(xp)
+        return x0
+
+
+class LongDPMGraph(_LongGraph, DPMGraph):
+    """DPMGraph for a long clip: gather + forward + blend, then vd_dpm_step (vd_cfg_stats +
+    vd_dpm_step_cfg guided) in place on the long latent and its x0 history."""
+
+    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0):
+        self._setup(model, sampler, windows, xt, guidance_scale, guidance_rescale)
+        self.coef, self.idx_all = sampler._tables(xt.device)
+        self.idx = self.idx_all[:1].clone()
+        # uninitialised on purpose: row 0 has C == 0 and does not read it
+        self.x0 = torch.empty_like(self.xt, memory_format=torch.contiguous_format)
+
+    def _body(self):
+        clip = self.sampler.clip_x0
+        eps = self.windows(self.xt, self.t)
+        if self.guided:
+            eps_c, eps_u = eps.chunk(2)
+            ops.dpm_step_cfg(self.xt, eps_c, eps_u, self.x0, self.coef, self.idx, self.scale,
+                             self.rescale, clip=clip, out=self.xt)
+        else:
+            ops.dpm_step(self.xt, eps, self.x0, self.coef, self.idx, clip=clip, out=self.xt)
+        return self.x0
+
+
+@torch.no_grad()
+def sample_long(model, sampler, cond, audio, shape, window, stride=None, blend="triangle",
+                window_batch=None, generator=None, callback=None, guidance_scale=1.0,
+                guidance_rescale=0.0):
+    """Sampling of a clip longer than the denoiser's window, with sample_ddim's contract:
+    returns (x_T_end, x0) of `shape` = (B, 3, L, H, W); `sampler` a DDIMSampler or a
+    DPMSolverSampler (TypeError otherwise); `audio` the L frames' windows or encoded features.
+
+    At every step the overlapping `window`-frame windows of the long latent (schedulers.
+    WindowPlan(L, window, stride, blend)) are denoised as one batched forward -- at most
+    `window_batch` windows at a time; None: all of them -- their predictions are blended where
+    they overlap with the plan's fixed weights, and the long latent is stepped once by the
+    sampler's own kernel, so guidance, its std-rescale over the whole clip, v-prediction and
+    the DPM-Solver++ history work as they do for a short clip.  The audio is encoded once for
+    the L frames and routed to the windows before the loop.  On a GPU one step is captured and
+    replayed (LongDDIMGraph / LongDPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which
+    launches the same kernels on the same operands).  L == window is one window: sample_ddim /
+    sample_dpm run as they are."""
+    from .schedulers import DDIMSampler, DPMSolverSampler, WindowPlan
+    if not isinstance(sampler, (DDIMSampler, DPMSolverSampler)):
+        raise TypeError(f"sample_long: sampler must be a DDIMSampler or a DPMSolverSampler, "
+                        f"got {type(sampler).__name__}")
+    if len(shape) != 5:
+        raise ValueError(f"sample_long: shape {tuple(shape)} is not (B, 3, L, H, W)")
+    plan = WindowPlan(shape[2], window, stride, blend)
+    if window_batch is not None and int(window_batch) < 1:
+        raise ValueError(f"sample_long: window_batch {window_batch} < 1")
+    dpm = isinstance(sampler, DPMSolverSampler)
+    if plan.num_windows == 1:
+        return (sample_dpm if dpm else sample_ddim)(
+            model, sampler, cond, audio, shape, generator=generator, callback=callback,
+            guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+    with ops.frozen_weights():
+        return _sample_long(model, sampler, dpm, plan, cond, audio, shape, window_batch,
+                            generator, callback, float(guidance_scale), float(guidance_rescale))
+
+
+def _sample_long(model, sampler, dpm, plan, cond, audio, shape, window_batch, generator,
+                 callback, scale, rescale):
+    model.eval()
+    device = cond.device
+    feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
+    xt = torch.randn(shape, generator=generator, device=device)
+    guided = scale != 1.0
+    windows = WindowedDenoiser(model, plan, cond, feats, xt, guided, window_batch)
+    x0 = None
+    graph = os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0" if dpm else _use_graph(device, sampler)
+    if device.type == "cuda" and graph:
+        g = (LongDPMGraph if dpm else LongDDIMGraph)(model, sampler, windows, xt, scale, rescale)
+        try:
+            g.capture()
+        except GraphUnsafe as e:
+            warnings.warn(f"{e}; sampling eagerly")
+            g = None
+        if g is not None:
+            for i in range(sampler.steps):
+                xt, x0 = g.step(i)
+                if callback is not None:  # the graph's static buffers: the next replay rewrites them
+                    callback(i, xt.clone(), x0.clone())
+            return xt.clone(), x0.clone()
+    kw = {}
+    for i in range(sampler.steps):
+        t = torch.full((windows.rows,), int(sampler.timesteps[i]), dtype=torch.int64,
+                       device=device)
+        if dpm:
+            kw = {"x0_last": x0}
+        if guided:
+            eps_c, eps_u = windows(xt, t).chunk(2)
+            xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale, **kw)
+        else:
+            xt, x0 = sampler.step(xt, windows(xt, t), i, **kw)
+        if callback is not None:  # DPM's x0 is the history buffer: the next step rewrites it
+            callback(i, xt, x0.clone() if dpm else x0)
+    return xt, x0
+
+
 @torch.no_grad()
 def sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps=None, generator=None,
                 callback=None, guidance_scale=1.0, guidance_rescale=0.0, prediction="eps"):

@@ -323,6 +323,63 @@ def dpm_step_cfg(xt, eps_c, eps_u, x0_hist, coef, step, scale, rescale=0.0, clip
     return xp, x0_hist
 
 
+def _window_args(name, long_, win, plan):
+    """Checked (B, C, HW) of a window op: `long_` [B, C, L, *spatial] and `win` [B * W, C, T,
+    *spatial] contiguous GPU tensors of one dtype that fit `plan` (a schedulers.WindowPlan)."""
+    _gpu(long_, win)
+    for what, t in (("the long tensor", long_), ("the window tensor", win)):
+        if t.dim() < 4 or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be contiguous [N, C, frames, *spatial], got "
+                             f"shape {tuple(t.shape)}, strides {tuple(t.stride())}")
+    B, C = long_.shape[:2]
+    if long_.shape[2] != plan.length:
+        raise ValueError(f"{name}: {long_.shape[2]} frames for a plan of {plan.length}")
+    want = (B * plan.num_windows, C, plan.window) + tuple(long_.shape[3:])
+    if tuple(win.shape) != want or win.dtype != long_.dtype:
+        raise ValueError(f"{name}: windows {tuple(win.shape)} {win.dtype} for a long tensor "
+                         f"{tuple(long_.shape)} {long_.dtype}: expected {want}")
+    return B, C, math.prod(long_.shape[3:])
+
+
+def window_gather(x, plan, out=None, dup=None):
+    """The plan's overlapping windows of a long latent (vd_window_gather): x [B, C, L, *spatial]
+    -> [B * W, C, T, *spatial], row b * W + w holding frames starts[w] .. starts[w] + T - 1 of
+    clip b.  out: the result's buffer; dup: a second buffer that receives the same values (the
+    null-audio half of a guided forward)."""
+    _gpu(x, out, dup)
+    if x.dim() < 4:
+        raise ValueError(f"window_gather: x must be [B, C, L, *spatial], got {tuple(x.shape)}")
+    shape = (x.shape[0] * plan.num_windows, x.shape[1], plan.window) + tuple(x.shape[3:])
+    win = torch.empty(shape, dtype=x.dtype, device=x.device) if out is None else out
+    B, C, HW = _window_args("window_gather", x, win, plan)
+    if dup is not None and (dup.shape != win.shape or dup.dtype != win.dtype
+                            or not dup.is_contiguous()):
+        raise ValueError("window_gather: `dup` must be a contiguous buffer like the windows")
+    starts, _, _ = plan._tables(x.device)
+    _lib.call("vd_window_gather", _p(x), _p(win), _p(dup), _p(starts), B, C, plan.length,
+              plan.window, plan.num_windows, HW, _dtype(x), _stream(x))
+    return win
+
+
+def window_blend(win, plan, out=None):
+    """The windows' values blended back into long tensors with the plan's fixed weights
+    (vd_window_blend): win [N * W, C, T, *spatial] -> [N, C, L, *spatial]; a frame's covering
+    windows are summed in ascending order in fp32 and rounded once.  out: the result's buffer."""
+    _gpu(win, out)
+    W = plan.num_windows
+    if win.dim() < 4 or win.shape[0] % W:
+        raise ValueError(f"window_blend: win must be [N * {W}, C, T, *spatial], got "
+                         f"{tuple(win.shape)}")
+    shape = (win.shape[0] // W, win.shape[1], plan.length) + tuple(win.shape[3:])
+    res = torch.empty(shape, dtype=win.dtype, device=win.device) if out is None else out
+    B, C, HW = _window_args("window_blend", res, win, plan)
+    starts, cover_win, cover_wgt = plan._tables(win.device)
+    _lib.call("vd_window_blend", _p(win), _p(res), _p(starts), _p(cover_win), _p(cover_wgt),
+              cover_win.shape[1], B, C, plan.length, plan.window, W, HW, _dtype(win),
+              _stream(win))
+    return res
+
+
 # --------------------------------------------------------------- GroupNorm+SiLU
 class GroupNormSiLUFn(torch.autograd.Function):
     """y = dropout(silu(GN(x))).  With `passthrough`, forward also returns x itself (an alias)

@@ -1,5 +1,6 @@
 """DDPM schedulers with the reference API (linear_noise_scheduler.py, noise_scheduler.py)
-plus a DDIM and a DPM-Solver++(2M) sampler, all running on the HIP scheduler kernels.
+plus a DDIM and a DPM-Solver++(2M) sampler, all running on the HIP scheduler kernels, and the
+window plan of long-clip sampling (WindowPlan).
 
 The schedule tables are built on the host exactly as the reference builds them (same
 torch CPU ops, so they are bit-identical and keep the reference attribute names);
@@ -156,6 +157,73 @@ class DDIMSampler:
                                  eps_u.contiguous().to(xt.dtype), t, tp, self._acp(xt.device),
                                  scale, rescale, eta=self.eta, z=z, clip=self.clip_x0,
                                  prediction=self.prediction)
+
+
+class WindowPlan:
+    """Overlapping temporal windows of a long clip and the fixed weights that blend them
+    (engine.sample_long; vd_window_gather / vd_window_blend): a clip of `length` = L frames is
+    covered by W = ceil((L - T) / S) + 1 windows of `window` = T frames that start every
+    `stride` = S frames (default T // 2; 1 <= S <= T), starts[w] = min(w S, L - T) -- the last
+    window is shifted back so that every window is full length; L == T is one window.
+
+    blend: the profile g[f] of a window's frame f, "triangle" (min(f + 1, T - f): a window
+    counts most at its centre, least at its ends) or "uniform" (1).  Frame l of the clip is
+    covered by the windows w_0 < w_1 < ... and takes their predictions with the weights
+    g[l - starts[w_k]] / sum_j g[l - starts[w_j]], computed in fp64 (self.weights64 [L, KMAX],
+    0 in the unused slots) and rounded once to fp32 (self.cover_wgt: the table the kernel reads,
+    as DPMSolverSampler.coef64 / coef); a frame covered once has the weight exactly 1.
+    self.cover_win [L, KMAX] int32 names the covering windows in ascending order, -1 in the
+    unused slots; KMAX = 8, and a plan that covers a frame more often is refused.
+    self.frame_index [W * T] int64 is the clip frame of every window frame, starts[w] + f: it
+    routes per-frame conditioning (the audio features) to the windows."""
+
+    KMAX = 8  # VD_WINDOW_KMAX
+    BLENDS = ("triangle", "uniform")
+
+    def __init__(self, length, window, stride=None, blend="triangle"):
+        L, T = int(length), int(window)
+        if T < 1:
+            raise ValueError(f"WindowPlan: window {window} < 1")
+        if L < T:
+            raise ValueError(f"WindowPlan: a clip of {length} frames is shorter than the window "
+                             f"of {window}")
+        S = T // 2 if stride is None else int(stride)
+        if stride is None and S < 1:
+            S = 1  # T == 1
+        if not 1 <= S <= T:
+            raise ValueError(f"WindowPlan: stride {stride} outside [1, window = {T}]")
+        if blend == "triangle":
+            g = [min(f + 1, T - f) for f in range(T)]
+        elif blend == "uniform":
+            g = [1] * T
+        else:
+            raise ValueError(f"WindowPlan: blend {blend!r}: 'triangle' or 'uniform'")
+        self.length, self.window, self.stride, self.blend = L, T, S, blend
+        self.num_windows = W = -(-(L - T) // S) + 1
+        starts = [min(w * S, L - T) for w in range(W)]
+        cover = [[w for w in range(W) if 0 <= l - starts[w] < T] for l in range(L)]
+        self.max_coverage = max(len(c) for c in cover)
+        if self.max_coverage > self.KMAX:
+            raise ValueError(f"WindowPlan: stride {S} covers a frame with {self.max_coverage} "
+                             f"windows of {T} frames, more than {self.KMAX}: use a larger stride")
+        self.starts = torch.tensor(starts, dtype=torch.int32)
+        self.cover_win = torch.full((L, self.KMAX), -1, dtype=torch.int32)
+        self.weights64 = torch.zeros((L, self.KMAX), dtype=torch.float64)
+        for l, ws in enumerate(cover):
+            gs = torch.tensor([g[l - starts[w]] for w in ws], dtype=torch.float64)
+            self.cover_win[l, :len(ws)] = torch.tensor(ws, dtype=torch.int32)
+            self.weights64[l, :len(ws)] = gs / gs.sum()
+        self.cover_wgt = self.weights64.float()
+        self.frame_index = (self.starts.long().view(W, 1) + torch.arange(T).view(1, T)).reshape(-1)
+        self._dev = {}
+
+    def _tables(self, device):
+        """(starts, cover_win, cover_wgt) on the device: the tables the kernels read."""
+        k = str(device)
+        if k not in self._dev:
+            self._dev[k] = tuple(t.to(device).contiguous()
+                                 for t in (self.starts, self.cover_win, self.cover_wgt))
+        return self._dev[k]
 
 
 def _prediction_keyword(init):

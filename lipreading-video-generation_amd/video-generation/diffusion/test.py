@@ -3,6 +3,8 @@
     python test.py [--ckpt model.pth | --random-init] [--sampler ddpm-v2|ddim|dpm++]
                    [--steps 500] [--spacing logsnr|linspace]
                    [--guidance-scale 1.0] [--guidance-rescale 0.0] [--prediction eps|v]
+                   [--clip-frames L] [--window-stride S] [--window-blend triangle|uniform]
+                   [--window-batch N]
 
 Reference API kept (importable without running anything, unlike the reference script):
   * `config` -- the dict of test.py:33-49 (same keys; `ldm_params` may also carry the
@@ -32,7 +34,8 @@ import numpy as np
 import torch
 
 import _vdiff_path  # noqa: F401
-from vdiff.engine import reinit_nonzero, sample_ddim, sample_dpm, synthetic_clip, v_to_eps
+from vdiff.engine import (reinit_nonzero, sample_ddim, sample_dpm, sample_long, synthetic_clip,
+                          v_to_eps)
 from vdiff.ops import cfg_combine, frozen_weights
 
 from linear_noise_scheduler import LinearNoiseSchedulerV2
@@ -199,10 +202,37 @@ def parse(argv=None):
     ap.add_argument("--prediction", default="eps", choices=["eps", "v"],
                     help="what the checkpoint's denoiser predicts (train.py --prediction); every "
                          "sampler reads its output accordingly")
+    ap.add_argument("--clip-frames", type=int, default=None,
+                    help="frames to generate (--dims 3; default --frames).  More than --frames: "
+                         "the clip is denoised as overlapping --frames windows blended at every "
+                         "step (--sampler ddim|dpm++)")
+    ap.add_argument("--window-stride", type=int, default=None,
+                    help="frames between window starts (default frames // 2)")
+    ap.add_argument("--window-blend", default="triangle", choices=["triangle", "uniform"],
+                    help="weights of overlapping windows: highest at a window's centre, or equal")
+    ap.add_argument("--window-batch", type=int, default=None,
+                    help="windows per denoiser forward (default: all of them in one)")
     args = ap.parse_args(argv)
     if args.steps is None and args.sampler == "dpm++":
         args.steps = 20
+    if args.clip_frames is not None:
+        if args.clip_frames < 1:
+            ap.error("--clip-frames must be at least 1")
+        _check_long(args, args.clip_frames)
     return args
+
+
+def _check_long(args, clip_frames):
+    """A clip longer than the denoiser's window needs the windowed samplers."""
+    if args.dims == 3 and clip_frames < args.frames:
+        raise SystemExit(f"test.py: a clip of {clip_frames} frames is shorter than the window "
+                         f"(--frames {args.frames})")
+    if clip_frames > (args.frames if args.dims == 3 else 1) and (
+            args.dims != 3 or args.sampler not in ("ddim", "dpm++")):
+        raise SystemExit(f"test.py: a clip of {clip_frames} frames is longer than the denoiser's "
+                         f"window (--frames {args.frames}); windowed sampling needs --dims 3 and "
+                         f"--sampler ddim or dpm++ (got --dims {args.dims}, --sampler "
+                         f"{args.sampler})")
 
 
 def main(argv=None):
@@ -223,12 +253,20 @@ def main(argv=None):
     config.update(cfg)
     model, scheduler = load_model_and_scheduler(config, seed=args.seed)
     frames = args.frames if args.dims == 3 else 1
+    clip_frames = frames if args.clip_frames is None else args.clip_frames
     if args.cond_npz:
         z = np.load(args.cond_npz, allow_pickle=False)
         cond = torch.from_numpy(z["image"]).float()[None].to(device)
         audio = {"input_values": torch.from_numpy(z["audio"]).float().to(device)}
+        if args.dims == 3 and audio["input_values"].shape[0] > frames:
+            # the file decides the clip's length: one frame per audio window
+            if args.clip_frames not in (None, audio["input_values"].shape[0]):
+                raise SystemExit(f"test.py: --clip-frames {args.clip_frames}, but {args.cond_npz} "
+                                 f"holds {audio['input_values'].shape[0]} audio windows")
+            clip_frames = audio["input_values"].shape[0]
+            _check_long(args, clip_frames)
     else:
-        clip = synthetic_clip(1, frames, args.image_size, 500, device, seed=args.seed,
+        clip = synthetic_clip(1, clip_frames, args.image_size, 500, device, seed=args.seed,
                               dims=args.dims)
         cond, audio = clip.cond, clip.audio
     g = torch.Generator(device=device).manual_seed(args.seed)
@@ -248,6 +286,15 @@ def main(argv=None):
             if (i + 1) % args.save_every == 0 or i == sampler.steps - 1:
                 save_frame(x0, os.path.join(args.out_dir, f"x0_{i}"))
 
+        if clip_frames > frames:  # (--dims 3: _check_long)
+            shape = (1, 3, clip_frames, args.image_size, args.image_size)
+            _, x0 = sample_long(model, sampler, cond, audio, shape, window=frames,
+                                stride=args.window_stride, blend=args.window_blend,
+                                window_batch=args.window_batch, generator=g, callback=cb,
+                                guidance_scale=args.guidance_scale,
+                                guidance_rescale=args.guidance_rescale)
+            print("All images have been processed and saved.")
+            return x0
         _, x0 = sample(model, sampler, cond, audio, shape, generator=g, callback=cb,
                        guidance_scale=args.guidance_scale,
                        guidance_rescale=args.guidance_rescale)
