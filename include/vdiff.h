@@ -303,6 +303,24 @@ int vd_groupnorm_silu_bwd_add(const void* x, const void* dy, const void* dadd,
                               const float* rstd, void* dx, float* dgamma, float* dbeta,
                               int B, int64_t S, int C, int G, int silu, float drop_p,
                               uint64_t seed, int dtype, void* workspace, void* stream);
+/* FiLM-conditioned GroupNorm (reference ResBlock, use_scale_shift_norm):
+ *   y = dropout(silu(GN(x) * (1 + scale[b, c]) + shift[b, c]))
+ * film is fp32 [B][2C], the scale in [:, :C] and the shift in [:, C:] (the layout of
+ * th.chunk(emb_out, 2, dim=1)).  The modulation folds into the per-(sample, channel) affine,
+ * so the launches, chunk plan, workspace and activation traffic are those of
+ * vd_groupnorm_silu_fwd / _bwd_add; film = 0 returns their bits.  The backward also writes
+ * dfilm (fp32 [B][2C], film's layout, every element OVERWRITTEN) in the finalize pass; all sums
+ * run in a fixed order (no atomics, no zero fill). */
+int vd_groupnorm_film_silu_fwd(const void* x, const float* gamma, const float* beta,
+                               const float* film, void* y, float* mean, float* rstd, int B,
+                               int64_t S, int C, int G, float eps, int silu, float drop_p,
+                               uint64_t seed, int dtype, void* workspace, void* stream);
+int vd_groupnorm_film_silu_bwd_add(const void* x, const void* dy, const void* dadd,
+                                   const float* gamma, const float* beta, const float* film,
+                                   const float* mean, const float* rstd, void* dx,
+                                   float* dgamma, float* dbeta, float* dfilm, int B, int64_t S,
+                                   int C, int G, int silu, float drop_p, uint64_t seed,
+                                   int dtype, void* workspace, void* stream);
 
 /* ---- SiLU on flat tensors (time-embedding MLP, ResBlock.emb_layers:
  * unet.py:483-487, 211-217).  bwd: dx = dy * silu'(x). */

@@ -91,6 +91,28 @@ struct Drop {
 
 static const uint64_t* g_drop_ctr = nullptr;  // vd_set_dropout_counter
 
+// FiLM conditioning (reference ResBlock, use_scale_shift_norm: out_norm(h) * (1 + scale) + shift):
+// film is fp32 [B][2C], scale in [:, :C], shift in [:, C:].  The modulation folds into the
+// channel affine, per (sample, channel):
+//   gamma' = gamma * (1 + s),  beta' = beta * (1 + s) + t
+// and every kernel below evaluates the plain expressions on gamma', beta' -- scale = shift = 0
+// gives gamma' = gamma, beta' = beta exactly, hence the plain kernels' bits.  FILM = false
+// never reads `film` (the plain entry points pass nullptr).
+template <bool FILM>
+__device__ __forceinline__ void gn_affine(const float* __restrict__ gamma,
+                                          const float* __restrict__ beta,
+                                          const float* __restrict__ film, int b, int C, int c,
+                                          float& ga, float& be) {
+  ga = gamma[c];
+  be = beta[c];
+  if constexpr (FILM) {
+    const float* f = film + (int64_t)b * 2 * C;
+    const float s1 = 1.f + f[c];
+    be = be * s1 + f[C + c];
+    ga = ga * s1;
+  }
+}
+
 // ---------------------------------------------------------------- forward
 // grid (nchunk, B).  Per WG: per-group (n, mean, M2) over its chunk.
 template <typename T, int U>
@@ -221,10 +243,11 @@ __global__ __launch_bounds__(kThreads) void gn_finalize_kernel(const float* __re
 // grid (nchunk, B): each thread keeps one 8-channel vector for all its pixel rows, so the
 // per-channel scale/shift (gamma * rstd, beta - mean * gamma * rstd) is computed once and
 // the loop is one FMA (+ SiLU, dropout) per element -- no index division per element.
-template <typename T, bool SILU, int U>
+template <typename T, bool SILU, int U, bool FILM>
 __global__ __launch_bounds__(kThreads) void gn_apply_kernel(const T* __restrict__ x,
                                                             const float* __restrict__ gamma,
                                                             const float* __restrict__ beta,
+                                                            const float* __restrict__ film,
                                                             const float* __restrict__ mean,
                                                             const float* __restrict__ rstd,
                                                             T* __restrict__ y, int64_t S, int C,
@@ -239,8 +262,10 @@ __global__ __launch_bounds__(kThreads) void gn_apply_kernel(const T* __restrict_
 #pragma unroll
   for (int j = 0; j < kVec; ++j) {
     const int c = cv * kVec + j, g = b * G + c / cpg;
-    sc[j] = gamma[c] * rstd[g];
-    sh[j] = beta[c] - mean[g] * sc[j];
+    float ga, be;
+    gn_affine<FILM>(gamma, beta, film, b, C, c, ga, be);
+    sc[j] = ga * rstd[g];
+    sh[j] = be - mean[g] * sc[j];
   }
   const int64_t p0 = (int64_t)blockIdx.x * chunk_px;
   int64_t p1 = p0 + chunk_px;
@@ -279,11 +304,11 @@ __global__ __launch_bounds__(kThreads) void gn_apply_kernel(const T* __restrict_
 
 // ---------------------------------------------------------------- backward
 // grid (nchunk, B): per-channel partial sums A = sum dz, Bs = sum dz * xhat
-template <typename T, bool SILU, int U>
+template <typename T, bool SILU, int U, bool FILM>
 __global__ __launch_bounds__(kThreads) void gn_bwd_reduce_kernel(
     const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
-    int64_t S, int C, int G, int64_t chunk_px, int rows_per_iter, float* __restrict__ part,
+    const float* __restrict__ beta, const float* __restrict__ film,
+    const float* __restrict__ mean, const float* __restrict__ rstd, int64_t S, int C, int G, int64_t chunk_px, int rows_per_iter, float* __restrict__ part,
     Drop drop_in) {
   const Drop drop = drop_in.resolved();
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -305,8 +330,7 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_reduce_kernel(
       const int c = cv * kVec + j;
       mu[j] = mean[b * G + c / cpg];
       rs[j] = rstd[b * G + c / cpg];
-      ga[j] = gamma[c];
-      be[j] = beta[c];
+      gn_affine<FILM>(gamma, beta, film, b, C, c, ga[j], be[j]);
       sa[j] = sb[j] = 0.f;
     }
     auto row = [&](int64_t p, const float* v, const float* d) {
@@ -408,11 +432,18 @@ __global__ __launch_bounds__(1024) void gn_bwd_sum_kernel(const float* __restric
 }
 
 // one WG: the ksplit slices of sums[z][b][c][2] added in order into slice 0, then group
-// coefficients per (b, g) and dgamma/dbeta per channel
+// coefficients per (b, g) and dgamma/dbeta per channel.  FILM: the group coefficients take
+// gamma'[b][c]; with A = sums[b][c][0], Bs = sums[b][c][1] and s1 = 1 + scale[b][c]
+//   dshift[b][c] = A,  dscale[b][c] = gamma[c] Bs + beta[c] A   (dfilm, film's layout)
+//   dbeta[c] = sum_b s1 A,  dgamma[c] = sum_b s1 Bs             (b ascending)
+// every element of dfilm is written (no zero fill).
+template <bool FILM>
 __global__ void gn_bwd_finalize_kernel(float* __restrict__ sums, int ksplit, int B, int C, int G,
                                        int64_t S, const float* __restrict__ gamma,
-                                       float* __restrict__ coef, float* __restrict__ dgamma,
-                                       float* __restrict__ dbeta) {
+                                       const float* __restrict__ beta,
+                                       const float* __restrict__ film, float* __restrict__ coef,
+                                       float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                       float* __restrict__ dfilm) {
   const int64_t slice = (int64_t)B * C * 2;
   for (int i = threadIdx.x; i < B * C; i += blockDim.x) {
     float a = sums[2 * i], s = sums[2 * i + 1];
@@ -432,8 +463,10 @@ __global__ void gn_bwd_finalize_kernel(float* __restrict__ sums, int ksplit, int
     float a = 0.f, s = 0.f;
     for (int k = 0; k < cpg; ++k) {
       const int c = g * cpg + k;
-      a += gamma[c] * sums[((int64_t)b * C + c) * 2];
-      s += gamma[c] * sums[((int64_t)b * C + c) * 2 + 1];
+      float ga = gamma[c];
+      if constexpr (FILM) ga = ga * (1.f + film[(int64_t)b * 2 * C + c]);
+      a += ga * sums[((int64_t)b * C + c) * 2];
+      s += ga * sums[((int64_t)b * C + c) * 2 + 1];
     }
     coef[bg * 2 + 0] = a * inv_n;
     coef[bg * 2 + 1] = s * inv_n;
@@ -441,19 +474,34 @@ __global__ void gn_bwd_finalize_kernel(float* __restrict__ sums, int ksplit, int
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float a = 0.f, s = 0.f;
     for (int b = 0; b < B; ++b) {
-      a += sums[((int64_t)b * C + c) * 2];
-      s += sums[((int64_t)b * C + c) * 2 + 1];
+      if constexpr (FILM) {
+        const float s1 = 1.f + film[(int64_t)b * 2 * C + c];
+        a += s1 * sums[((int64_t)b * C + c) * 2];
+        s += s1 * sums[((int64_t)b * C + c) * 2 + 1];
+      } else {
+        a += sums[((int64_t)b * C + c) * 2];
+        s += sums[((int64_t)b * C + c) * 2 + 1];
+      }
     }
     dbeta[c] = a;
     dgamma[c] = s;
   }
+  if constexpr (FILM) {
+    for (int i = threadIdx.x; i < B * C; i += blockDim.x) {
+      const int b = i / C, c = i % C;
+      const float a = sums[2 * (int64_t)i], bs = sums[2 * (int64_t)i + 1];
+      dfilm[(int64_t)b * 2 * C + c] = gamma[c] * bs + beta[c] * a;
+      dfilm[(int64_t)b * 2 * C + C + c] = a;
+    }
+  }
 }
 
 // grid (nchunk, B), per-thread channel constants as gn_apply_kernel
-template <typename T, bool SILU, int U>
+template <typename T, bool SILU, int U, bool FILM>
 __global__ __launch_bounds__(kThreads) void gn_bwd_apply_kernel(
     const T* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ rstd,
+    const float* __restrict__ beta, const float* __restrict__ film,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ coef, const T* __restrict__ dadd, T* __restrict__ dx, int64_t S,
     int C, int G, int64_t chunk_px, int rows_per_iter, Drop drop_in) {
   const Drop drop = drop_in.resolved();
@@ -467,8 +515,7 @@ __global__ __launch_bounds__(kThreads) void gn_bwd_apply_kernel(
     const int c = cv * kVec + j, g = b * G + c / cpg;
     mu[j] = mean[g];
     rs[j] = rstd[g];
-    ga[j] = gamma[c];
-    be[j] = beta[c];
+    gn_affine<FILM>(gamma, beta, film, b, C, c, ga[j], be[j]);
     c0[j] = coef[2 * g];
     c1[j] = coef[2 * g + 1];
   }
@@ -532,6 +579,101 @@ int gn_check(const void* x, int B, int64_t S, int C, int G) {
   return VD_OK;
 }
 
+// the launches of vd_groupnorm_silu_fwd (FILM = false) / vd_groupnorm_film_silu_fwd: the same
+// chunk plan, workspace and U dispatch for both
+template <bool FILM>
+int gn_fwd(const void* x, const float* gamma, const float* beta, const float* film, void* y,
+           float* mean, float* rstd, int B, int64_t S, int C, int G, float eps, int silu,
+           float drop_p, uint64_t seed, int dtype, void* workspace, void* stream) {
+  int rc = gn_check(x, B, S, C, G);
+  if (rc) return rc;
+  VD_REQUIRE(gamma && beta && y && mean && rstd && workspace, "null argument");
+  VD_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "dropout p=%f out of [0, 1)", drop_p);
+  VD_REQUIRE(drop_p == 0.f || silu, "dropout is fused only after SiLU");
+  const Drop drop{drop_p, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed, g_drop_ctr};
+  GNPlan p = gn_plan(B, S, C);
+  float* part = reinterpret_cast<float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const size_t lds = (size_t)p.rows_per_iter * C * sizeof(Stat);
+  const dim3 grid(p.nchunk, B);
+#define VD_GN_FWD(U)                                                                             \
+  gn_stats_kernel<T, U><<<grid, kThreads, lds, st>>>((const T*)x, S, C, G, p.chunk_px,          \
+                                                     p.rows_per_iter, part);                    \
+  gn_finalize_kernel<<<dim3(G, B), kThreads, 0, st>>>(part, p.nchunk, G, eps, mean, rstd);     \
+  if (silu)                                                                                      \
+    gn_apply_kernel<T, true, U, FILM><<<grid, kThreads, 0, st>>>(                                \
+        (const T*)x, gamma, beta, film, mean, rstd, (T*)y, S, C, G, p.chunk_px,                  \
+        p.rows_per_iter, drop);                                                                  \
+  else                                                                                           \
+    gn_apply_kernel<T, false, U, FILM><<<grid, kThreads, 0, st>>>(                               \
+        (const T*)x, gamma, beta, film, mean, rstd, (T*)y, S, C, G, p.chunk_px,                  \
+        p.rows_per_iter, drop)
+  const int u = g_gn_unroll.load(std::memory_order_relaxed);
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (u == 4) {
+      VD_GN_FWD(4);
+    } else if (u == 2) {
+      VD_GN_FWD(2);
+    } else {
+      VD_GN_FWD(1);
+    }
+  });
+#undef VD_GN_FWD
+}
+
+template <bool FILM>
+int gn_bwd(const void* x, const void* dy, const void* dadd, const float* gamma, const float* beta,
+           const float* film, const float* mean, const float* rstd, void* dx, float* dgamma,
+           float* dbeta, float* dfilm, int B, int64_t S, int C, int G, int silu, float drop_p,
+           uint64_t seed, int dtype, void* workspace, void* stream) {
+  int rc = gn_check(x, B, S, C, G);
+  if (rc) return rc;
+  VD_REQUIRE(dy && gamma && beta && mean && rstd && dx && dgamma && dbeta && workspace,
+             "null argument");
+  VD_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "dropout p=%f out of [0, 1)", drop_p);
+  const Drop drop{drop_p, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed, g_drop_ctr};
+  GNPlan p = gn_plan(B, S, C);
+  float* part = reinterpret_cast<float*>(workspace);
+  float* coef = part + (size_t)B * p.nchunk * C * 2;
+  float* sums = coef + (size_t)B * G * 2;
+  hipStream_t st = VD_STREAM(stream);
+  const size_t lds = (size_t)p.rows_per_iter * C * sizeof(float2);
+  const dim3 grid(p.nchunk, B);
+  const int ksplit = (int)vd_cdiv(p.nchunk, kSumPer);
+#define VD_GN_BWD(U)                                                                             \
+  if (silu)                                                                                      \
+    gn_bwd_reduce_kernel<T, true, U, FILM><<<grid, kThreads, lds, st>>>(                         \
+        (const T*)x, (const T*)dy, gamma, beta, film, mean, rstd, S, C, G, p.chunk_px,           \
+        p.rows_per_iter, part, drop);                                                            \
+  else                                                                                           \
+    gn_bwd_reduce_kernel<T, false, U, FILM><<<grid, kThreads, lds, st>>>(                        \
+        (const T*)x, (const T*)dy, gamma, beta, film, mean, rstd, S, C, G, p.chunk_px,           \
+        p.rows_per_iter, part, drop);                                                            \
+  gn_bwd_sum_kernel<<<dim3((unsigned)vd_cdiv(C, 64), B, ksplit), 1024, 0, st>>>(                \
+      part, p.nchunk, C, kSumPer, sums);                                                         \
+  gn_bwd_finalize_kernel<FILM><<<1, kThreads, 0, st>>>(sums, ksplit, B, C, G, S, gamma, beta,    \
+                                                       film, coef, dgamma, dbeta, dfilm);        \
+  if (silu)                                                                                      \
+    gn_bwd_apply_kernel<T, true, U, FILM><<<grid, kThreads, 0, st>>>(                            \
+        (const T*)x, (const T*)dy, gamma, beta, film, mean, rstd, coef, (const T*)dadd, (T*)dx,  \
+        S, C, G, p.chunk_px, p.rows_per_iter, drop);                                             \
+  else                                                                                           \
+    gn_bwd_apply_kernel<T, false, U, FILM><<<grid, kThreads, 0, st>>>(                           \
+        (const T*)x, (const T*)dy, gamma, beta, film, mean, rstd, coef, (const T*)dadd, (T*)dx,  \
+        S, C, G, p.chunk_px, p.rows_per_iter, drop)
+  const int u = g_gn_unroll.load(std::memory_order_relaxed);
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (u == 4) {
+      VD_GN_BWD(4);
+    } else if (u == 2) {
+      VD_GN_BWD(2);
+    } else {
+      VD_GN_BWD(1);
+    }
+  });
+#undef VD_GN_BWD
+}
+
 }  // namespace
 
 extern "C" {
@@ -560,40 +702,17 @@ int vd_groupnorm_silu_fwd(const void* x, const float* gamma, const float* beta, 
                           float* mean, float* rstd, int B, int64_t S, int C, int G, float eps,
                           int silu, float drop_p, uint64_t seed, int dtype, void* workspace,
                           void* stream) {
-  int rc = gn_check(x, B, S, C, G);
-  if (rc) return rc;
-  VD_REQUIRE(gamma && beta && y && mean && rstd && workspace, "null argument");
-  VD_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "dropout p=%f out of [0, 1)", drop_p);
-  VD_REQUIRE(drop_p == 0.f || silu, "dropout is fused only after SiLU");
-  const Drop drop{drop_p, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed, g_drop_ctr};
-  GNPlan p = gn_plan(B, S, C);
-  float* part = reinterpret_cast<float*>(workspace);
-  hipStream_t st = VD_STREAM(stream);
-  const size_t lds = (size_t)p.rows_per_iter * C * sizeof(Stat);
-  const dim3 grid(p.nchunk, B);
-#define VD_GN_FWD(U)                                                                             \
-  gn_stats_kernel<T, U><<<grid, kThreads, lds, st>>>((const T*)x, S, C, G, p.chunk_px,          \
-                                                     p.rows_per_iter, part);                    \
-  gn_finalize_kernel<<<dim3(G, B), kThreads, 0, st>>>(part, p.nchunk, G, eps, mean, rstd);     \
-  if (silu)                                                                                      \
-    gn_apply_kernel<T, true, U><<<grid, kThreads, 0, st>>>((const T*)x, gamma, beta, mean,      \
-                                                           rstd, (T*)y, S, C, G, p.chunk_px,    \
-                                                           p.rows_per_iter, drop);              \
-  else                                                                                           \
-    gn_apply_kernel<T, false, U><<<grid, kThreads, 0, st>>>((const T*)x, gamma, beta, mean,     \
-                                                            rstd, (T*)y, S, C, G, p.chunk_px,   \
-                                                            p.rows_per_iter, drop)
-  const int u = g_gn_unroll.load(std::memory_order_relaxed);
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (u == 4) {
-      VD_GN_FWD(4);
-    } else if (u == 2) {
-      VD_GN_FWD(2);
-    } else {
-      VD_GN_FWD(1);
-    }
-  });
-#undef VD_GN_FWD
+  return gn_fwd<false>(x, gamma, beta, nullptr, y, mean, rstd, B, S, C, G, eps, silu, drop_p,
+                       seed, dtype, workspace, stream);
+}
+
+int vd_groupnorm_film_silu_fwd(const void* x, const float* gamma, const float* beta,
+                               const float* film, void* y, float* mean, float* rstd, int B,
+                               int64_t S, int C, int G, float eps, int silu, float drop_p,
+                               uint64_t seed, int dtype, void* workspace, void* stream) {
+  VD_REQUIRE(film, "null film");
+  return gn_fwd<true>(x, gamma, beta, film, y, mean, rstd, B, S, C, G, eps, silu, drop_p, seed,
+                      dtype, workspace, stream);
 }
 
 int vd_groupnorm_silu_bwd(const void* x, const void* dy, const float* gamma, const float* beta,
@@ -609,52 +728,19 @@ int vd_groupnorm_silu_bwd_add(const void* x, const void* dy, const void* dadd, c
                               float* dgamma, float* dbeta, int B, int64_t S, int C, int G,
                               int silu, float drop_p, uint64_t seed, int dtype, void* workspace,
                               void* stream) {
-  int rc = gn_check(x, B, S, C, G);
-  if (rc) return rc;
-  VD_REQUIRE(dy && gamma && beta && mean && rstd && dx && dgamma && dbeta && workspace,
-             "null argument");
-  VD_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "dropout p=%f out of [0, 1)", drop_p);
-  const Drop drop{drop_p, drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f, seed, g_drop_ctr};
-  GNPlan p = gn_plan(B, S, C);
-  float* part = reinterpret_cast<float*>(workspace);
-  float* coef = part + (size_t)B * p.nchunk * C * 2;
-  float* sums = coef + (size_t)B * G * 2;
-  hipStream_t st = VD_STREAM(stream);
-  const size_t lds = (size_t)p.rows_per_iter * C * sizeof(float2);
-  const dim3 grid(p.nchunk, B);
-  const int ksplit = (int)vd_cdiv(p.nchunk, kSumPer);
-#define VD_GN_BWD(U)                                                                             \
-  if (silu)                                                                                      \
-    gn_bwd_reduce_kernel<T, true, U><<<grid, kThreads, lds, st>>>(                               \
-        (const T*)x, (const T*)dy, gamma, beta, mean, rstd, S, C, G, p.chunk_px,                 \
-        p.rows_per_iter, part, drop);                                                            \
-  else                                                                                           \
-    gn_bwd_reduce_kernel<T, false, U><<<grid, kThreads, lds, st>>>(                              \
-        (const T*)x, (const T*)dy, gamma, beta, mean, rstd, S, C, G, p.chunk_px,                 \
-        p.rows_per_iter, part, drop);                                                            \
-  gn_bwd_sum_kernel<<<dim3((unsigned)vd_cdiv(C, 64), B, ksplit), 1024, 0, st>>>(                \
-      part, p.nchunk, C, kSumPer, sums);                                                         \
-  gn_bwd_finalize_kernel<<<1, kThreads, 0, st>>>(sums, ksplit, B, C, G, S, gamma, coef, dgamma,  \
-                                                 dbeta);                                          \
-  if (silu)                                                                                      \
-    gn_bwd_apply_kernel<T, true, U><<<grid, kThreads, 0, st>>>(                                  \
-        (const T*)x, (const T*)dy, gamma, beta, mean, rstd, coef, (const T*)dadd, (T*)dx, S, C,  \
-        G, p.chunk_px, p.rows_per_iter, drop);                                                   \
-  else                                                                                           \
-    gn_bwd_apply_kernel<T, false, U><<<grid, kThreads, 0, st>>>(                                 \
-        (const T*)x, (const T*)dy, gamma, beta, mean, rstd, coef, (const T*)dadd, (T*)dx, S, C,  \
-        G, p.chunk_px, p.rows_per_iter, drop)
-  const int u = g_gn_unroll.load(std::memory_order_relaxed);
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (u == 4) {
-      VD_GN_BWD(4);
-    } else if (u == 2) {
-      VD_GN_BWD(2);
-    } else {
-      VD_GN_BWD(1);
-    }
-  });
-#undef VD_GN_BWD
+  return gn_bwd<false>(x, dy, dadd, gamma, beta, nullptr, mean, rstd, dx, dgamma, dbeta, nullptr,
+                       B, S, C, G, silu, drop_p, seed, dtype, workspace, stream);
+}
+
+int vd_groupnorm_film_silu_bwd_add(const void* x, const void* dy, const void* dadd,
+                                   const float* gamma, const float* beta, const float* film,
+                                   const float* mean, const float* rstd, void* dx, float* dgamma,
+                                   float* dbeta, float* dfilm, int B, int64_t S, int C, int G,
+                                   int silu, float drop_p, uint64_t seed, int dtype,
+                                   void* workspace, void* stream) {
+  VD_REQUIRE(film && dfilm, "null film / dfilm");
+  return gn_bwd<true>(x, dy, dadd, gamma, beta, film, mean, rstd, dx, dgamma, dbeta, dfilm, B, S,
+                      C, G, silu, drop_p, seed, dtype, workspace, stream);
 }
 
 }  // extern "C"

@@ -63,6 +63,8 @@ def unet_forward_work(model, x_shape, audio_tokens=12) -> Work:
         for layer in seq:
             pix = T * state["H"] * state["W"]
             if isinstance(layer, ResBlock):
+                # the same with use_scale_shift_norm: the two convs and the skip are unchanged,
+                # and the (then twice as wide) embedding GEMM was never counted
                 _conv(w, B, pix, layer.out_channels, layer.channels, k)
                 _conv(w, B, pix, layer.out_channels, layer.out_channels, k)
                 if layer.out_channels != layer.channels:

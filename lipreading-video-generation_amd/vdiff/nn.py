@@ -221,7 +221,9 @@ class ResBlock(TimestepBlock):
 
     forward = conv2(dropout(silu(GN2(conv1(silu(GN1(x))) + emb_layers(emb))))) + skip(x)
     with GN+SiLU(+dropout) fused, the emb add fused into conv1's epilogue and the skip
-    add fused into conv2's epilogue.
+    add fused into conv2's epilogue.  With use_scale_shift_norm (unet.py:253-257) emb_layers
+    gives [scale | shift] and the middle is silu(GN2(conv1(..)) * (1 + scale) + shift), the
+    modulation folded into the GroupNorm kernels (ops.group_norm_film_silu).
     """
 
     def __init__(self, channels, emb_channels, dropout, out_channels=None, use_conv=False,
@@ -234,15 +236,17 @@ class ResBlock(TimestepBlock):
         self.use_conv = use_conv
         self.use_checkpoint = use_checkpoint
         self.use_scale_shift_norm = use_scale_shift_norm
-        if use_scale_shift_norm or up or down:
-            raise NotImplementedError("use_scale_shift_norm / resblock_updown are not used by "
-                                      "the reference train.py/test.py path and not accelerated")
+        if up or down:
+            raise NotImplementedError("ResBlock up / down (resblock_updown) need the avg-pool "
+                                      "Downsample, which is not on the accelerated path")
         self.in_layers = nn.Sequential(
             normalization(channels), SiLU(),
             conv_nd(dims, channels, self.out_channels, 3, padding=1))
         self.updown = False
         self.h_upd = self.x_upd = nn.Identity()
-        self.emb_layers = nn.Sequential(SiLU(), linear(emb_channels, self.out_channels))
+        self.emb_layers = nn.Sequential(
+            SiLU(), linear(emb_channels,
+                           2 * self.out_channels if use_scale_shift_norm else self.out_channels))
         self.out_layers = nn.Sequential(
             normalization(self.out_channels), SiLU(), nn.Dropout(p=dropout),
             zero_module(conv_nd(dims, self.out_channels, self.out_channels, 3, padding=1)))
@@ -262,9 +266,16 @@ class ResBlock(TimestepBlock):
         # x also feeds the skip branch: its two gradients meet inside GN1's backward
         h, xs = ops.group_norm_silu_pass(x, gn1.weight, gn1.bias, gn1.num_groups, gn1.eps)
         emb_out = emb[self] if isinstance(emb, EmbTable) else self.emb_layers(emb)
-        h = ops.conv(h, conv1.weight, conv1.bias, conv1.stride, conv1.padding, chan_add=emb_out)
         p = drop.p if self.training else 0.0
-        h = ops.group_norm_silu(h, gn2.weight, gn2.bias, gn2.num_groups, gn2.eps, dropout=p)
+        if self.use_scale_shift_norm:
+            # emb_out = [scale | shift]: GN2(h) * (1 + scale) + shift inside the GN kernels
+            h = ops.conv(h, conv1.weight, conv1.bias, conv1.stride, conv1.padding)
+            h = ops.group_norm_film_silu(h, gn2.weight, gn2.bias, emb_out, gn2.num_groups,
+                                         gn2.eps, dropout=p)
+        else:
+            h = ops.conv(h, conv1.weight, conv1.bias, conv1.stride, conv1.padding,
+                         chan_add=emb_out)
+            h = ops.group_norm_silu(h, gn2.weight, gn2.bias, gn2.num_groups, gn2.eps, dropout=p)
         skip = self.skip_connection(xs)
         return ops.conv(h, conv2.weight, conv2.bias, conv2.stride, conv2.padding, residual=skip)
 

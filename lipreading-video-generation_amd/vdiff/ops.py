@@ -459,6 +459,72 @@ def group_norm_silu_pass(x, weight, bias, groups=32, eps=1e-5, silu=True):
 _GN_PASSTHROUGH = os.environ.get("VDIFF_GN_PASSTHROUGH", "1") != "0"
 
 
+class GroupNormFiLMSiLUFn(torch.autograd.Function):
+    """y = dropout(silu(GN(x) * (1 + scale) + shift)), film = [scale | shift] of shape [B, 2C]
+    (reference ResBlock with use_scale_shift_norm, unet.py:253-257).  The modulation folds into
+    the kernels' per-(sample, channel) affine: the launches and the activation traffic are
+    GroupNormSiLUFn's, and film's gradient comes out of the backward's finalize pass.
+    `passthrough` as in GroupNormSiLUFn (x's other gradient joins inside the last pass)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, film, groups: int, eps: float, silu: bool, drop_p: float,
+                seed: int, passthrough: bool = False):
+        _gpu(x, gamma, beta, film)
+        x = to_cl(x)
+        B, Cc, S = x.shape[0], x.shape[1], _spatial(x)
+        if film.numel() != B * 2 * Cc or film.shape[0] != B:
+            raise ValueError(f"film shape {list(film.shape)} != [{B}, {2 * Cc}]")
+        dt = _dtype(x)
+        g32 = gamma.detach().float().contiguous()
+        b32 = beta.detach().float().contiguous()
+        f32 = film.detach().float().reshape(B, 2 * Cc).contiguous()
+        y = torch.empty_like(x)
+        mean = torch.empty(B * groups, dtype=torch.float32, device=x.device)
+        rstd = torch.empty_like(mean)
+        ws = torch.empty(_lib.lib().vd_groupnorm_workspace_size(B, S, Cc, groups),
+                         dtype=torch.uint8, device=x.device)
+        _lib.call("vd_groupnorm_film_silu_fwd", _p(x), _p(g32), _p(b32), _p(f32), _p(y),
+                  _p(mean), _p(rstd), B, S, Cc, groups, float(eps), int(silu), float(drop_p),
+                  int(seed), dt, _p(ws), _stream(x))
+        ctx.save_for_backward(x, g32, b32, f32, mean, rstd)
+        ctx.cfg = (groups, silu, gamma.dtype, float(drop_p), int(seed), film.dtype, film.shape)
+        if passthrough:
+            return y, x.view_as(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy, dadd=None):
+        x, g32, b32, f32, mean, rstd = ctx.saved_tensors
+        groups, silu, pdt, drop_p, seed, fdt, fshape = ctx.cfg
+        dy = to_cl(dy).to(x.dtype)
+        if dadd is not None:
+            dadd = to_cl(dadd).to(x.dtype)
+            if dadd.stride() != x.stride():
+                dadd = torch.empty_like(x).copy_(dadd)
+        B, Cc, S = x.shape[0], x.shape[1], _spatial(x)
+        dx = torch.empty_like(x)
+        dg = torch.empty(Cc, dtype=torch.float32, device=x.device)
+        db = torch.empty_like(dg)
+        df = torch.empty_like(f32)
+        ws = torch.empty(_lib.lib().vd_groupnorm_workspace_size(B, S, Cc, groups),
+                         dtype=torch.uint8, device=x.device)
+        _lib.call("vd_groupnorm_film_silu_bwd_add", _p(x), _p(dy), _p(dadd), _p(g32), _p(b32),
+                  _p(f32), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), _p(df), B, S, Cc, groups,
+                  int(silu), drop_p, seed, _dtype(x), _p(ws), _stream(x))
+        return (dx, dg.to(pdt), db.to(pdt), df.reshape(fshape).to(fdt), None, None, None, None,
+                None, None)
+
+
+def group_norm_film_silu(x, weight, bias, film, groups=32, eps=1e-5, silu=True, dropout=0.0,
+                         seed=None):
+    """silu(GroupNorm(x) * (1 + film[:, :C]) + film[:, C:]) [then train-mode dropout]; film is
+    [B, 2C] in any float dtype (read as fp32; its gradient returns in its own dtype)."""
+    if dropout > 0.0 and seed is None:
+        seed = new_seed()
+    return GroupNormFiLMSiLUFn.apply(x, weight, bias, film, groups, eps, silu, float(dropout),
+                                     int(seed or 0))
+
+
 class SiLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

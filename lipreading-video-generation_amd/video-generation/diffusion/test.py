@@ -80,11 +80,16 @@ def load_model_and_scheduler(config, *, seed=0):
         attention_mode=lp.get("attention_mode", "joint"),
         use_bf16=lp.get("dtype", "bf16") == "bf16",
         audio_attention=lp.get("audio_attention", False),
+        use_scale_shift_norm=lp.get("use_scale_shift_norm", False),
         # with a checkpoint the wav2vec2 weights come from it; without one the random
         # encoder is the explicitly requested smoke mode
         audio_encoder_pretrained=False)
     if ckpt:
         sd = torch.load(ckpt, map_location="cpu", weights_only=True)
+        if "model" in sd and "epoch" in sd:  # a train.py resume file: it records the flag
+            from train import check_resume_scale_shift_norm
+            check_resume_scale_shift_norm(sd, lp.get("use_scale_shift_norm", False))
+            sd = sd["model"]
         model.load_state_dict(_strip_module(sd))
     else:
         warnings.warn("test.py: no checkpoint (ldm_ckpt_name is None): seeded smoke weights "
@@ -202,6 +207,9 @@ def parse(argv=None):
     ap.add_argument("--prediction", default="eps", choices=["eps", "v"],
                     help="what the checkpoint's denoiser predicts (train.py --prediction); every "
                          "sampler reads its output accordingly")
+    ap.add_argument("--use-scale-shift-norm", action="store_true",
+                    help="the checkpoint's ResBlocks are FiLM-conditioned (train.py "
+                         "--use-scale-shift-norm)")
     ap.add_argument("--clip-frames", type=int, default=None,
                     help="frames to generate (--dims 3; default --frames).  More than --frames: "
                          "the clip is denoised as overlapping --frames windows blended at every "
@@ -248,7 +256,8 @@ def main(argv=None):
     cfg = {k: dict(v) for k, v in config.items()}
     cfg["dataset_params"]["im_size"] = args.image_size
     cfg["ldm_params"].update(dims=args.dims, attention_mode=args.attention_mode,
-                             dtype=args.dtype, audio_attention=args.audio_attention)
+                             dtype=args.dtype, audio_attention=args.audio_attention,
+                             use_scale_shift_norm=args.use_scale_shift_norm)
     cfg["train_params"]["ldm_ckpt_name"] = args.ckpt
     config.update(cfg)
     model, scheduler = load_model_and_scheduler(config, seed=args.seed)
