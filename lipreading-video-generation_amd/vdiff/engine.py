@@ -1,11 +1,10 @@
-"""Training step and samplers around the drop-in model (the loops of the reference
-train.py:107-134 and test.py:51-83), plus synthetic clip generation.
+"""Training step around the drop-in model (the loop of the reference train.py:107-134), plus
+synthetic clip generation.  The samplers live in vdiff.sampling; their public names are
+re-exported here.
 
-Differences from the reference loops (all deliberate):
+Differences from the reference loop (all deliberate):
   * t ~ U{0, ..., num_timesteps-1}: the reference draws randint(0, 500) against a
     100-step schedule (train.py:125) and crashes;
-  * no per-step torch.cuda.empty_cache() in sampling (test.py:58), and the audio
-    encoder runs once per clip instead of at every denoising step;
   * gradients are averaged across ranks by vdiff.ddp.GradBucketer (world > 1).
 """
 from __future__ import annotations
@@ -13,7 +12,6 @@ from __future__ import annotations
 import contextlib
 import math
 import os
-import warnings
 import weakref
 from dataclasses import dataclass
 
@@ -21,6 +19,10 @@ import torch
 
 from . import hipgraph, ops
 from .ddp import GradBucketer
+from .sampling import (DDIMGraph, DPMGraph, GraphUnsafe, LongDDIMGraph,  # noqa: F401
+                       LongDPMGraph, WindowedDenoiser, sample_ddim, sample_ddpm, sample_dpm,
+                       sample_long, v_to_eps)
+from .schedulers import _sqrt_tables
 
 
 @dataclass
@@ -72,19 +74,6 @@ def audio_keep_mask(batch, p, device, generator=None):
         raise ValueError(f"audio_drop_prob {p} outside [0, 1]")
     u = torch.rand((batch,), generator=generator, device=device)
     return (u >= p).to(torch.float32)
-
-
-def _sqrt_tables(scheduler):
-    """(sqrt_acp, sqrt_1m_acp) of a DDPM scheduler as fp32 CPU vectors: the two tables its
-    q_sample reads, under either family's attribute names."""
-    for names in (("sqrt_alpha_cum_prod", "sqrt_one_minus_alpha_cum_prod"),
-                  ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")):
-        if all(hasattr(scheduler, n) for n in names):
-            return tuple(getattr(scheduler, n).detach().float().cpu().contiguous()
-                         for n in names)
-    raise ValueError(f"{type(scheduler).__name__} has no sqrt_alpha_cum_prod / "
-                     "sqrt_one_minus_alpha_cum_prod tables: a non-default objective and "
-                     "v-prediction sampling read them")
 
 
 class Trainer:
@@ -583,521 +572,3 @@ class TrainStepGraph:
                    if p.requires_grad and id(p) not in enc_ids and p.grad is None]
         if missing:  # a parameter off the captured path would silently never train
             raise RuntimeError(f"TrainStepGraph: no captured gradient for {missing[:4]}")
-
-
-@torch.no_grad()
-def sample_ddim(model, sampler, cond, audio, shape, generator=None, callback=None,
-                guidance_scale=1.0, guidance_rescale=0.0):
-    """DDIM sampling (build extension of test.py:51-83): audio encoded once, packed conv
-    weights reused across steps (ops.frozen_weights).
-
-    guidance_scale w != 1: classifier-free audio guidance.  Each step runs one forward at batch
-    2B -- rows [0, B) with the encoded audio, rows [B, 2B) with the null audio (zeros, what
-    Trainer(audio_drop_prob=...) trains on) -- and steps on eps_u + w (eps_c - eps_u),
-    std-rescaled per sample by guidance_rescale (Lin et al. 2023; 0 = off).  w == 1 is the
-    unguided path, unchanged."""
-    with ops.frozen_weights():
-        return _sample_ddim(model, sampler, cond, audio, shape, generator, callback,
-                            float(guidance_scale), float(guidance_rescale))
-
-
-def _doubled(cond, feats):
-    """The conditioning of a guided forward at batch 2B: cond repeated, and the encoded audio
-    followed by the null audio (zeros of the same shape)."""
-    return torch.cat([cond, cond]), torch.cat([feats, torch.zeros_like(feats)])
-
-
-class GraphUnsafe(RuntimeError):
-    """A captured graph holds a node type that is not safe to replay (a memset node)."""
-
-
-class DDIMGraph:
-    """One deterministic DDIM denoising step -- UNet forward + vd_ddim_step -- captured once
-    as a HIP graph and replayed per step (no per-kernel launch gaps, no host work per
-    step).  The sample lives in a static buffer updated in place; the step's timesteps are
-    copied device-to-device from the sampler's table before each replay.  Use inside
-    ops.frozen_weights() (the graph reads the cached packed conv weights); eta must be 0.
-
-    guidance_scale != 1 (classifier-free audio guidance): the captured step is the UNet forward
-    at batch 2B + vd_cfg_stats (guidance_rescale > 0) + vd_ddim_step_cfg.  The model's output is
-    read as sampler.prediction says ("eps" or "v"; the same launches either way).  The graph owns a
-    static [2B, ...] input whose halves are the fused kernel's x_prev and x_prev_dup, so the
-    doubled input stays current without a copy; the doubled cond / audio / timestep buffers and
-    the null audio are built here, before capture (no memset node in the step)."""
-
-    def __init__(self, model, sampler, cond, feats, xt, guidance_scale=1.0, guidance_rescale=0.0):
-        if sampler.eta != 0:
-            raise ValueError("DDIMGraph: eta = 0 (deterministic DDIM) only")
-        dev = xt.device
-        B = xt.shape[0]
-        self.model, self.sampler = model, sampler
-        self.scale, self.rescale = float(guidance_scale), float(guidance_rescale)
-        self.guided = self.scale != 1.0
-        if self.guided:
-            cond, feats = _doubled(cond, feats)
-            self.x2 = torch.cat([xt, xt])
-            self.xt, self.xdup = self.x2[:B], self.x2[B:]
-            B = 2 * B  # rows of the timestep buffers (the step kernel reads the first half)
-        else:
-            self.xt = xt.clone()
-        self.cond, self.feats = cond, feats
-        self.t_all = sampler.timesteps.to(dev).view(-1, 1).expand(-1, B).contiguous()
-        self.tp_all = sampler.prev_timesteps.to(dev).view(-1, 1).expand(-1, B).contiguous()
-        self.t = self.t_all[0].clone()
-        self.tp = self.tp_all[0].clone()
-        self.acp = sampler._acp(dev)
-        self.graph = None
-        self.x0 = None
-
-    def _body(self):
-        if self.guided:
-            B = self.xt.shape[0]
-            eps = self.model(self.x2, self.cond, self.feats, self.t)
-            eps_c, eps_u = eps.to(self.xt.dtype).chunk(2)
-            _, x0 = ops.ddim_step_cfg(self.xt, eps_c, eps_u, self.t[:B], self.tp[:B], self.acp,
-                                      self.scale, self.rescale, clip=self.sampler.clip_x0,
-                                      out=self.xt, dup=self.xdup,
-                                      prediction=self.sampler.prediction)
-            return x0
-        eps = self.model(self.xt, self.cond, self.feats, self.t)
-        xp, x0 = ops.ddim_step(self.xt, eps.to(self.xt.dtype), self.t, self.tp, self.acp,
-                               eta=0.0, clip=self.sampler.clip_x0,
-                               prediction=self.sampler.prediction)
-        self.xt.copy_(xp.view_as(self.xt))
-        return x0
-
-    def capture(self):
-        """Warm up eagerly and capture one step (step() does this on first use).  Raises
-        GraphUnsafe if the captured step holds a memset node."""
-        cur = torch.cuda.current_stream()
-        side = torch.cuda.Stream(device=self.xt.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):  # eager warm-up: packed weights, tables, workspaces
-            buf = self.x2 if self.guided else self.xt
-            keep = buf.clone()
-            self._body()
-            buf.copy_(keep)
-        cur.wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph(keep_graph=True)  # node list kept (node_types)
-        with hipgraph.capture(self.graph):
-            self.x0 = self._body()
-        self.graph.instantiate()
-        types = self.node_types()
-        if types.get("memset", 0):
-            # DESIGN section 9.3: a memset node replayed with eager work between replays is
-            # where a captured reduction went stale on this HIP runtime; sample() steps
-            # eagerly instead of trusting such a graph
-            raise GraphUnsafe(f"{type(self).__name__}: captured step holds memset nodes {types}")
-
-    def node_types(self):
-        """{node type: count} of the captured step (vdiff.hipgraph; memset nodes must be 0)."""
-        return hipgraph.node_counts(self.graph)
-
-    def step(self, i):
-        """Denoise from sampler.timesteps[i]; returns (x_prev, x0) (static buffers)."""
-        self.t.copy_(self.t_all[i])
-        self.tp.copy_(self.tp_all[i])
-        if self.graph is None:
-            self.capture()
-        self.graph.replay()
-        return self.xt, self.x0.view_as(self.xt)
-
-
-def _use_graph(device, sampler):
-    return (device.type == "cuda" and sampler.eta == 0
-            and os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0")
-
-
-def _sample_ddim(model, sampler, cond, audio, shape, generator, callback, scale=1.0,
-                 rescale=0.0):
-    model.eval()
-    device = cond.device
-    feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
-    xt = torch.randn(shape, generator=generator, device=device)
-    x0 = None
-    if _use_graph(device, sampler):
-        g = DDIMGraph(model, sampler, cond, feats, xt, scale, rescale)
-        try:
-            g.capture()
-        except GraphUnsafe as e:
-            warnings.warn(f"{e}; sampling eagerly")
-            g = None
-        if g is not None:
-            for i in range(sampler.steps):
-                xt, x0 = g.step(i)
-                if callback is not None:  # the graph's static buffers: the next replay rewrites them
-                    callback(i, xt.clone(), x0.clone())
-            return xt.clone(), x0.clone()
-    guided = scale != 1.0
-    if guided:
-        cond, feats = _doubled(cond, feats)
-    nb = (2 if guided else 1) * shape[0]
-    for i in range(sampler.steps):
-        t = torch.full((nb,), int(sampler.timesteps[i]), dtype=torch.int64, device=device)
-        if guided:
-            eps_c, eps_u = model(torch.cat([xt, xt]), cond, feats, t).chunk(2)
-            xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale)
-        else:
-            xt, x0 = sampler.step(xt, model(xt, cond, feats, t), i)
-        if callback is not None:
-            callback(i, xt, x0)
-    return xt, x0
-
-
-class DPMGraph(DDIMGraph):
-    """One DPM-Solver++(2M) step -- UNet forward + vd_dpm_step, or at batch 2B + vd_cfg_stats +
-    vd_dpm_step_cfg when guided -- captured once and replayed for every step: the kernel picks
-    its coefficient row by a device scalar, so the first-order, second-order and last steps
-    differ only in the table.  On top of DDIMGraph's static sample the graph owns the x0
-    history (read as the previous step's x0, written in place; x_prev is written over xt) and
-    the step-index scalar, copied device-to-device before each replay like the timesteps."""
-
-    def __init__(self, model, sampler, cond, feats, xt, guidance_scale=1.0, guidance_rescale=0.0):
-        dev = xt.device
-        B = xt.shape[0]
-        self.model, self.sampler = model, sampler
-        self.scale, self.rescale = float(guidance_scale), float(guidance_rescale)
-        self.guided = self.scale != 1.0
-        if self.guided:
-            cond, feats = _doubled(cond, feats)
-            self.x2 = torch.cat([xt, xt])
-            self.xt, self.xdup = self.x2[:B], self.x2[B:]
-            B = 2 * B
-        else:
-            self.xt = xt.clone()
-        self.cond, self.feats = cond, feats
-        self.t_all = sampler.timesteps.to(dev).view(-1, 1).expand(-1, B).contiguous()
-        self.t = self.t_all[0].clone()
-        self.coef, self.idx_all = sampler._tables(dev)
-        self.idx = self.idx_all[:1].clone()
-        # uninitialised on purpose: row 0 has C == 0 and does not read it
-        self.x0 = torch.empty_like(self.xt, memory_format=torch.contiguous_format)
-        self.graph = None
-
-    def _body(self):
-        clip = self.sampler.clip_x0
-        if self.guided:
-            eps = self.model(self.x2, self.cond, self.feats, self.t)
-            eps_c, eps_u = eps.to(self.xt.dtype).chunk(2)
-            ops.dpm_step_cfg(self.xt, eps_c, eps_u, self.x0, self.coef, self.idx, self.scale,
-                             self.rescale, clip=clip, out=self.xt, dup=self.xdup)
-        else:
-            eps = self.model(self.xt, self.cond, self.feats, self.t)
-            ops.dpm_step(self.xt, eps.to(self.xt.dtype), self.x0, self.coef, self.idx,
-                         clip=clip, out=self.xt)
-        return self.x0
-
-    def step(self, i):
-        """Denoise from sampler.timesteps[i]; returns (x_prev, x0) (static buffers).  Steps run
-        in order: step i reads the x0 that step i - 1 left in the history."""
-        self.t.copy_(self.t_all[i])
-        self.idx.copy_(self.idx_all[i:i + 1])
-        if self.graph is None:
-            self.capture()
-        self.graph.replay()
-        return self.xt, self.x0
-
-
-@torch.no_grad()
-def sample_dpm(model, sampler, cond, audio, shape, generator=None, callback=None,
-               guidance_scale=1.0, guidance_rescale=0.0):
-    """DPM-Solver++(2M) sampling (schedulers.DPMSolverSampler) with sample_ddim's contract:
-    audio encoded once, packed conv weights reused across the steps, callback(i, xt, x0) at
-    every step, classifier-free audio guidance as one forward at batch 2B, and on a GPU one
-    replayed graph (DPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which launches the same
-    kernels on the same operands)."""
-    with ops.frozen_weights():
-        return _sample_dpm(model, sampler, cond, audio, shape, generator, callback,
-                           float(guidance_scale), float(guidance_rescale))
-
-
-def _sample_dpm(model, sampler, cond, audio, shape, generator, callback, scale=1.0, rescale=0.0):
-    model.eval()
-    device = cond.device
-    feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
-    xt = torch.randn(shape, generator=generator, device=device)
-    x0 = None
-    if device.type == "cuda" and os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0":
-        g = DPMGraph(model, sampler, cond, feats, xt, scale, rescale)
-        try:
-            g.capture()
-        except GraphUnsafe as e:
-            warnings.warn(f"{e}; sampling eagerly")
-            g = None
-        if g is not None:
-            for i in range(sampler.steps):
-                xt, x0 = g.step(i)
-                if callback is not None:  # the graph's static buffers: the next replay rewrites them
-                    callback(i, xt.clone(), x0.clone())
-            return xt.clone(), x0.clone()
-    guided = scale != 1.0
-    if guided:
-        cond, feats = _doubled(cond, feats)
-    nb = (2 if guided else 1) * shape[0]
-    for i in range(sampler.steps):
-        t = torch.full((nb,), int(sampler.timesteps[i]), dtype=torch.int64, device=device)
-        if guided:
-            eps_c, eps_u = model(torch.cat([xt, xt]), cond, feats, t).chunk(2)
-            xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale, x0_last=x0)
-        else:
-            xt, x0 = sampler.step(xt, model(xt, cond, feats, t), i, x0_last=x0)
-        if callback is not None:  # x0 is the history buffer: the next step rewrites it
-            callback(i, xt, x0.clone())
-    return xt, x0
-
-
-class WindowedDenoiser:
-    """The denoiser applied to a long latent through the overlapping windows of a
-    schedulers.WindowPlan: gather the windows (vd_window_gather), run the model on them as one
-    batch (or in chunks of at most `window_batch` windows), blend the predictions back into the
-    long clip (vd_window_blend).  Everything a step needs is built here, before the loop and
-    before any capture: the per-frame audio features routed to the windows by plan.frame_index,
-    cond repeated per window, the null audio of a guided run (zeros) and the static window
-    buffer.  Guided, the window batch is [B * W with the audio; B * W with the null audio], the
-    second half filled by the gather's `dup`, and the blend runs over 2B clips: chunk(2) of the
-    result is (eps_c, eps_u) on the long clip."""
-
-    def __init__(self, model, plan, cond, feats, xt, guided=False, window_batch=None):
-        B, C, L = xt.shape[:3]
-        W, T = plan.num_windows, plan.window
-        if L != plan.length:
-            raise ValueError(f"sample_long: {L} frames for a plan of {plan.length}")
-        if cond.shape[0] != B or feats.shape[0] != B * L:
-            raise ValueError(f"sample_long: cond {tuple(cond.shape)} / encoded audio "
-                             f"{tuple(feats.shape)} do not fit {B} clips of {L} frames (one "
-                             "reference image per clip, one audio window per frame)")
-        if window_batch is not None and int(window_batch) < 1:
-            raise ValueError(f"sample_long: window_batch {window_batch} < 1")
-        dev = xt.device
-        rows = (torch.arange(B, device=dev).view(B, 1) * L
-                + plan.frame_index.to(dev).view(1, W * T)).reshape(-1)
-        feats = feats.index_select(0, rows)              # [B * W * T, ...]
-        cond = cond.repeat_interleave(W, dim=0)          # [B * W, ...]
-        if guided:
-            cond, feats = _doubled(cond, feats)
-        self.model, self.plan, self.guided = model, plan, guided
-        self.cond, self.feats = cond, feats
-        self.half = B * W
-        self.rows = (2 if guided else 1) * B * W         # of the window batch and its timesteps
-        self.chunk = self.rows if window_batch is None else min(int(window_batch), self.rows)
-        self.win = torch.empty((self.rows, C, T) + tuple(xt.shape[3:]), dtype=xt.dtype,
-                               device=dev)
-
-    def __call__(self, xt, t):
-        """The model's output on the long clip: [B, ...] like xt, or [2B, ...] guided.  t: the
-        window batch's timesteps, [self.rows]."""
-        n, T = self.half, self.plan.window
-        ops.window_gather(xt, self.plan, out=self.win[:n],
-                          dup=self.win[n:] if self.guided else None)
-        outs = []
-        for i in range(0, self.rows, self.chunk):
-            j = min(i + self.chunk, self.rows)
-            outs.append(self.model(self.win[i:j], self.cond[i:j], self.feats[i * T:j * T],
-                                   t[i:j]))
-        eps = outs[0] if len(outs) == 1 else torch.cat(outs)
-        return ops.window_blend(eps.to(xt.dtype).contiguous(), self.plan)
-
-
-class _LongGraph:
-    """Buffer setup of the long-clip graphs: the long latent and its history are static, the
-    model input is WindowedDenoiser's window buffer, and the timestep buffers have one row per
-    window of the batch (B * W, or 2 B * W guided) -- the step kernels read the first B."""
-
-    def _setup(self, model, sampler, windows, xt, guidance_scale, guidance_rescale):
-        self.model, self.sampler, self.windows = model, sampler, windows
-        self.scale, self.rescale = float(guidance_scale), float(guidance_rescale)
-        self.guided = windows.guided
-        self.xt = xt.clone()
-        # the buffer capture() saves and restores around its warm-up: the long latent itself
-        # (the window buffer is rewritten from it by every step's gather)
-        self.x2 = self.xt
-        self.cond, self.feats = windows.cond, windows.feats
-        self.t_all = sampler.timesteps.to(xt.device).view(-1, 1).expand(-1, windows.rows) \
-            .contiguous()
-        self.t = self.t_all[0].clone()
-        self.graph = None
-
-
-class LongDDIMGraph(_LongGraph, DDIMGraph):
-    """DDIMGraph for a long clip: the captured step is gather + the UNet forward at batch B * W
-    (2 B * W guided) + blend + the same vd_ddim_step / vd_cfg_stats + vd_ddim_step_cfg launches
-    on the long tensors."""
-
-    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0):
-        if sampler.eta != 0:
-            raise ValueError("LongDDIMGraph: eta = 0 (deterministic DDIM) only")
-        self._setup(model, sampler, windows, xt, guidance_scale, guidance_rescale)
-        self.tp_all = sampler.prev_timesteps.to(xt.device).view(-1, 1) \
-            .expand(-1, windows.rows).contiguous()
-        self.tp = self.tp_all[0].clone()
-        self.acp = sampler._acp(xt.device)
-        self.x0 = None
-
-    def _body(self):
-        B = self.xt.shape[0]
-        eps = self.windows(self.xt, self.t)
-        if self.guided:
-            eps_c, eps_u = eps.chunk(2)
-            _, x0 = ops.ddim_step_cfg(self.xt, eps_c, eps_u, self.t[:B], self.tp[:B], self.acp,
-                                      self.scale, self.rescale, clip=self.sampler.clip_x0,
-                                      out=self.xt, prediction=self.sampler.prediction)
-            return x0
-        xp, x0 = ops.ddim_step(self.xt, eps, self.t[:B], self.tp[:B], self.acp, eta=0.0,
-                               clip=self.sampler.clip_x0, prediction=self.sampler.prediction)
-        self.xt.copy_(xp)
-        return x0
-
-
-class LongDPMGraph(_LongGraph, DPMGraph):
-    """DPMGraph for a long clip: gather + forward + blend, then vd_dpm_step (vd_cfg_stats +
-    vd_dpm_step_cfg guided) in place on the long latent and its x0 history."""
-
-    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0):
-        self._setup(model, sampler, windows, xt, guidance_scale, guidance_rescale)
-        self.coef, self.idx_all = sampler._tables(xt.device)
-        self.idx = self.idx_all[:1].clone()
-        # uninitialised on purpose: row 0 has C == 0 and does not read it
-        self.x0 = torch.empty_like(self.xt, memory_format=torch.contiguous_format)
-
-    def _body(self):
-        clip = self.sampler.clip_x0
-        eps = self.windows(self.xt, self.t)
-        if self.guided:
-            eps_c, eps_u = eps.chunk(2)
-            ops.dpm_step_cfg(self.xt, eps_c, eps_u, self.x0, self.coef, self.idx, self.scale,
-                             self.rescale, clip=clip, out=self.xt)
-        else:
-            ops.dpm_step(self.xt, eps, self.x0, self.coef, self.idx, clip=clip, out=self.xt)
-        return self.x0
-
-
-@torch.no_grad()
-def sample_long(model, sampler, cond, audio, shape, window, stride=None, blend="triangle",
-                window_batch=None, generator=None, callback=None, guidance_scale=1.0,
-                guidance_rescale=0.0):
-    """Sampling of a clip longer than the denoiser's window, with sample_ddim's contract:
-    returns (x_T_end, x0) of `shape` = (B, 3, L, H, W); `sampler` a DDIMSampler or a
-    DPMSolverSampler (TypeError otherwise); `audio` the L frames' windows or encoded features.
-
-    At every step the overlapping `window`-frame windows of the long latent (schedulers.
-    WindowPlan(L, window, stride, blend)) are denoised as one batched forward -- at most
-    `window_batch` windows at a time; None: all of them -- their predictions are blended where
-    they overlap with the plan's fixed weights, and the long latent is stepped once by the
-    sampler's own kernel, so guidance, its std-rescale over the whole clip, v-prediction and
-    the DPM-Solver++ history work as they do for a short clip.  The audio is encoded once for
-    the L frames and routed to the windows before the loop.  On a GPU one step is captured and
-    replayed (LongDDIMGraph / LongDPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which
-    launches the same kernels on the same operands).  L == window is one window: sample_ddim /
-    sample_dpm run as they are."""
-    from .schedulers import DDIMSampler, DPMSolverSampler, WindowPlan
-    if not isinstance(sampler, (DDIMSampler, DPMSolverSampler)):
-        raise TypeError(f"sample_long: sampler must be a DDIMSampler or a DPMSolverSampler, "
-                        f"got {type(sampler).__name__}")
-    if len(shape) != 5:
-        raise ValueError(f"sample_long: shape {tuple(shape)} is not (B, 3, L, H, W)")
-    plan = WindowPlan(shape[2], window, stride, blend)
-    if window_batch is not None and int(window_batch) < 1:
-        raise ValueError(f"sample_long: window_batch {window_batch} < 1")
-    dpm = isinstance(sampler, DPMSolverSampler)
-    if plan.num_windows == 1:
-        return (sample_dpm if dpm else sample_ddim)(
-            model, sampler, cond, audio, shape, generator=generator, callback=callback,
-            guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
-    with ops.frozen_weights():
-        return _sample_long(model, sampler, dpm, plan, cond, audio, shape, window_batch,
-                            generator, callback, float(guidance_scale), float(guidance_rescale))
-
-
-def _sample_long(model, sampler, dpm, plan, cond, audio, shape, window_batch, generator,
-                 callback, scale, rescale):
-    model.eval()
-    device = cond.device
-    feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
-    xt = torch.randn(shape, generator=generator, device=device)
-    guided = scale != 1.0
-    windows = WindowedDenoiser(model, plan, cond, feats, xt, guided, window_batch)
-    x0 = None
-    graph = os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0" if dpm else _use_graph(device, sampler)
-    if device.type == "cuda" and graph:
-        g = (LongDPMGraph if dpm else LongDDIMGraph)(model, sampler, windows, xt, scale, rescale)
-        try:
-            g.capture()
-        except GraphUnsafe as e:
-            warnings.warn(f"{e}; sampling eagerly")
-            g = None
-        if g is not None:
-            for i in range(sampler.steps):
-                xt, x0 = g.step(i)
-                if callback is not None:  # the graph's static buffers: the next replay rewrites them
-                    callback(i, xt.clone(), x0.clone())
-            return xt.clone(), x0.clone()
-    kw = {}
-    for i in range(sampler.steps):
-        t = torch.full((windows.rows,), int(sampler.timesteps[i]), dtype=torch.int64,
-                       device=device)
-        if dpm:
-            kw = {"x0_last": x0}
-        if guided:
-            eps_c, eps_u = windows(xt, t).chunk(2)
-            xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale, **kw)
-        else:
-            xt, x0 = sampler.step(xt, windows(xt, t), i, **kw)
-        if callback is not None:  # DPM's x0 is the history buffer: the next step rewrites it
-            callback(i, xt, x0.clone() if dpm else x0)
-    return xt, x0
-
-
-@torch.no_grad()
-def sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps=None, generator=None,
-                callback=None, guidance_scale=1.0, guidance_rescale=0.0, prediction="eps"):
-    """Ancestral sampling as test.py:51-83 (V2 scheduler by default there).  guidance_scale !=
-    1: classifier-free audio guidance as in sample_ddim; the guided noise (ops.cfg_combine) is
-    the eps of the scheduler's p_sample kernel.  prediction="v": the model's (guided) output is
-    v, and eps = sqrt_1m_acp[t] xt + sqrt_acp[t] v is formed by one extra launch per step --
-    ops.q_sample(v, xt, t, ...) on the scheduler's own tables -- before the unchanged p_sample
-    kernel."""
-    ops.prediction_id(prediction)
-    with ops.frozen_weights():
-        return _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator,
-                            callback, float(guidance_scale), float(guidance_rescale), prediction)
-
-
-def v_to_eps(scheduler, v, xt, t):
-    """eps = sqrt_1m_acp[t] xt + sqrt_acp[t] v of a v-prediction model's output, in xt's dtype:
-    vd_q_sample with v in x0's place and xt in the noise's."""
-    sa, s1m = _v_tables(scheduler, xt.device)
-    return ops.q_sample(v.contiguous().to(xt.dtype), xt.contiguous(), t, sa, s1m)
-
-
-def _v_tables(scheduler, device):
-    cache = scheduler.__dict__.setdefault("_v_tables_dev", {})
-    key = str(device)
-    if key not in cache:
-        cache[key] = tuple(v.to(device) for v in _sqrt_tables(scheduler))
-    return cache[key]
-
-
-def _sample_ddpm(model, scheduler, cond, audio, shape, n_timesteps, generator, callback,
-                 scale=1.0, rescale=0.0, prediction="eps"):
-    model.eval()
-    device = cond.device
-    feats = model.encode_audio(audio) if hasattr(model, "encode_audio") else audio
-    n = n_timesteps or scheduler.num_timesteps
-    xt = torch.randn(shape, generator=generator, device=device)
-    x0 = None
-    if scale != 1.0:
-        cond2, feats2 = _doubled(cond, feats)
-    for i in reversed(range(n)):
-        t = torch.full((shape[0],), i, dtype=torch.int64, device=device)
-        if scale != 1.0:
-            eps_c, eps_u = model(torch.cat([xt, xt]), cond2, feats2, torch.cat([t, t])).chunk(2)
-            eps = ops.cfg_combine(eps_c, eps_u, scale, rescale)
-        else:
-            eps = model(xt, cond, feats, t)
-        if prediction == "v":
-            eps = v_to_eps(scheduler, eps, xt, t)
-        z = torch.randn(xt.shape, generator=generator, device=device)
-        xt, x0 = scheduler.sample_prev_timestep(xt, eps, t, z=z)
-        if callback is not None:
-            callback(i, xt, x0)
-    return xt, x0

@@ -28,6 +28,19 @@ class _Tables:
         return cache[key]
 
 
+def _sqrt_tables(scheduler):
+    """(sqrt_acp, sqrt_1m_acp) of a DDPM scheduler as fp32 CPU vectors: the two tables its
+    q_sample reads, under either family's attribute names."""
+    for names in (("sqrt_alpha_cum_prod", "sqrt_one_minus_alpha_cum_prod"),
+                  ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")):
+        if all(hasattr(scheduler, n) for n in names):
+            return tuple(getattr(scheduler, n).detach().float().cpu().contiguous()
+                         for n in names)
+    raise ValueError(f"{type(scheduler).__name__} has no sqrt_alpha_cum_prod / "
+                     "sqrt_one_minus_alpha_cum_prod tables: a non-default objective and "
+                     "v-prediction sampling read them")
+
+
 class LinearNoiseScheduler(_Tables):
     """linear_noise_scheduler.py:6-76 (DDPM, standard posterior variance)."""
 
@@ -134,11 +147,14 @@ class DDIMSampler:
             self._acp_dev[k] = self.acp.to(device).contiguous()
         return self._acp_dev[k]
 
+    def _t_tp(self, xt, i):
+        """Step i's timestep and previous timestep, one row per sample of xt."""
+        return tuple(torch.full((xt.shape[0],), int(ts[i]), dtype=torch.int64, device=xt.device)
+                     for ts in (self.timesteps, self.prev_timesteps))
+
     def step(self, xt, noise_pred, i, z=None):
         """One update from self.timesteps[i] to self.prev_timesteps[i]: (x_prev, x0)."""
-        B = xt.shape[0]
-        t = torch.full((B,), int(self.timesteps[i]), dtype=torch.int64, device=xt.device)
-        tp = torch.full((B,), int(self.prev_timesteps[i]), dtype=torch.int64, device=xt.device)
+        t, tp = self._t_tp(xt, i)
         if self.eta > 0 and z is None:
             z = torch.randn_like(xt)
         return ops.ddim_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), t, tp,
@@ -148,9 +164,7 @@ class DDIMSampler:
     def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, z=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
         by `rescale`: guide, rescale and update in one kernel (ops.ddim_step_cfg)."""
-        B = xt.shape[0]
-        t = torch.full((B,), int(self.timesteps[i]), dtype=torch.int64, device=xt.device)
-        tp = torch.full((B,), int(self.prev_timesteps[i]), dtype=torch.int64, device=xt.device)
+        t, tp = self._t_tp(xt, i)
         if self.eta > 0 and z is None:
             z = torch.randn_like(xt)
         return ops.ddim_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
@@ -161,7 +175,7 @@ class DDIMSampler:
 
 class WindowPlan:
     """Overlapping temporal windows of a long clip and the fixed weights that blend them
-    (engine.sample_long; vd_window_gather / vd_window_blend): a clip of `length` = L frames is
+    (sampling.sample_long; vd_window_gather / vd_window_blend): a clip of `length` = L frames is
     covered by W = ceil((L - T) / S) + 1 windows of `window` = T frames that start every
     `stride` = S frames (default T // 2; 1 <= S <= T), starts[w] = min(w S, L - T) -- the last
     window is shifted back so that every window is full length; L == T is one window.
@@ -341,32 +355,33 @@ class DPMSolverSampler:
                             torch.arange(self.steps, dtype=torch.int64, device=device))
         return self._dev[k]
 
-    def _hist(self, xt, i, x0_last):
+    def _row(self, xt, i, x0_last):
+        """What step i's kernel reads besides xt and the model's output: (x0 history buffer,
+        coefficient table, device index of row i).  Without x0_last the buffer is new and
+        uninitialised, which only a row that does not read it (C == 0) may have."""
+        i = int(i)
         if not 0 <= i < self.steps:
             raise IndexError(f"DPMSolverSampler: step {i} outside [0, {self.steps})")
-        if x0_last is not None:
-            return x0_last
-        if float(self.coef[i, 4]) != 0.0:
-            raise ValueError(f"DPMSolverSampler: step {i} is a second-order row and needs "
-                             "x0_last, the x0 that step i - 1 returned")
-        return torch.empty_like(xt, memory_format=torch.contiguous_format)
+        if x0_last is None:
+            if float(self.coef[i, 4]) != 0.0:
+                raise ValueError(f"DPMSolverSampler: step {i} is a second-order row and needs "
+                                 "x0_last, the x0 that step i - 1 returned")
+            x0_last = torch.empty_like(xt, memory_format=torch.contiguous_format)
+        coef, idx = self._tables(xt.device)
+        return x0_last, coef, idx[i:i + 1]
 
     def step(self, xt, noise_pred, i, x0_last=None):
         """One update from self.timesteps[i] to self.prev_timesteps[i]: (x_prev, x0).  x0_last:
         the x0 that step i - 1 returned; it is overwritten in place with this step's x0 and
         returned.  None is allowed where the row does not read it (C == 0)."""
-        i = int(i)
-        hist = self._hist(xt, i, x0_last)
-        coef, idx = self._tables(xt.device)
+        hist, coef, idx = self._row(xt, i, x0_last)
         return ops.dpm_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), hist, coef,
-                            idx[i:i + 1], clip=self.clip_x0)
+                            idx, clip=self.clip_x0)
 
     def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, x0_last=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
         by `rescale`: guide, rescale and update in one kernel (ops.dpm_step_cfg)."""
-        i = int(i)
-        hist = self._hist(xt, i, x0_last)
-        coef, idx = self._tables(xt.device)
+        hist, coef, idx = self._row(xt, i, x0_last)
         return ops.dpm_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
-                                eps_u.contiguous().to(xt.dtype), hist, coef, idx[i:i + 1], scale,
+                                eps_u.contiguous().to(xt.dtype), hist, coef, idx, scale,
                                 rescale, clip=self.clip_x0)
