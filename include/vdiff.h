@@ -364,8 +364,11 @@ int vd_upsample_nearest_hw_bwd(const void* dy, void* dx, int B, int T, int H,
  *   bwd_wgt  : dw    [Co][taps][Ci] fp32, ACCUMULATED into (zero it first)
  * Epilogue of fwd: y = conv + bias[co] + chan_add[b][co] + residual.
  * Any of bias / chan_add / residual may be NULL.  bias/chan_add are fp32;
- * residual has the activation dtype and y's shape.
- * Ci must be a multiple of 8 (bf16) or 4 (fp32); pad channels otherwise. */
+ * residual has the activation dtype, y's shape and y's pixel stride (y_cstride).
+ * Ci must be a multiple of 8 in both dtypes (the kernels read 16-byte bf16 chunks and the
+ * fp32 path keeps the same rule); pad channels otherwise.  x_cstride must be a multiple of 8;
+ * y_cstride may be any value >= Co for the forward and must be a multiple of 8, like Co, for
+ * bwd_data and bwd_weight, which read dy in 16-byte chunks. */
 typedef struct vd_conv_desc {
   int B;
   int Ti, Hi, Wi, Ci;  /* input  */

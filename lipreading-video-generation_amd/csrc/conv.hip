@@ -2329,6 +2329,7 @@ static int wgrad_run(const vd_conv_desc* d, const void* x, const void* dy, float
   if (rc) return rc;
   VD_REQUIRE(dry || (x && dy && dw), "null tensor");
   VD_REQUIRE(d->Co % 8 == 0, "bwd_weight needs Co %% 8 == 0 (got %d)", d->Co);
+  VD_REQUIRE(d->y_cstride == 0 || d->y_cstride % 8 == 0, "bad y_cstride");  // dy in 16-B chunks
   WgtGeom g;
   g.split_stride = split_stride;
   g.xcd_tiles = g.xcd_total = 0;
