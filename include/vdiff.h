@@ -61,6 +61,16 @@ int vd_timestep_embedding_tab(const int64_t* t, int B, int dim, const float* fre
  * x tensors are [B][per_sample] in `dtype`.  z may be NULL where the
  * formula adds no noise.
  *
+ * Alignment of the per-sample kernels -- ONE rule for every entry point of this group:
+ * vd_q_sample, vd_p_sample_v1 / _v2 / _cosine, vd_ddim_step / _pred, vd_cfg_stats,
+ * vd_cfg_combine, vd_ddim_step_cfg / _cfg_pred, vd_dpm_step / _cfg.  A call moves 8 elements
+ * per lane (16-byte accesses) when per_sample % 8 == 0 AND every non-null tensor pointer it is
+ * given (inputs, outputs, the duplicate, the history) is 16-byte aligned; any other call runs
+ * one element at a time, so element-aligned pointers are always legal.  Both paths perform the
+ * same fp32 operations per element.  Tables, t / t_prev / step and the statistics workspace
+ * need their natural alignment only.  (vd_mse_loss / _bwd, below, are stricter: they refuse
+ * unaligned tensors with VD_EINVAL.)
+ *
  * q_sample: linear_noise_scheduler.py:24-46 (add_noise)
  *   xt = sqrt_acp[t] * x0 + sqrt_1m_acp[t] * eps */
 int vd_q_sample(const void* x0, const void* eps, void* xt, const int64_t* t,
@@ -146,7 +156,8 @@ int vd_p_sample_cosine(const void* xt, const void* eps, const void* z,
  * x0 = (xt - sqrt(1-a_t) eps)/sqrt(a_t) [clamped to [-1,1] if clip];
  * sigma = eta sqrt((1-a_p)/(1-a_t) (1 - a_t/a_p));
  * x_prev = sqrt(a_p) x0 + sqrt(1-a_p-sigma^2) eps + sigma z, a_p = acp[t_prev]
- * or 1 when t_prev < 0.  t, t_prev: int64[B]. */
+ * or 1 when t_prev < 0.  t, t_prev: int64[B].  x0 (the second output) may be NULL, here and
+ * in vd_ddim_step_pred: it is then not written.  z may be NULL when eta == 0. */
 int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev,
                  void* x0, const int64_t* t, const int64_t* t_prev,
                  const float* acp, float eta, int clip, int64_t B,
@@ -665,8 +676,12 @@ int vd_cross_attention_bwd_dkdv(const vd_xattn_desc* x, const void* q, const voi
  * 22-bit fixed-point coefficients int[out][ksize], ksize = 2 * ceil(in / out) + 1 (<= cap).
  * vd_frames_resize_normalize (GPU): uint8 frames [n][H][W][3] -> horizontal pass into tmp
  * (uint8 [n][H][OW][3]) -> vertical pass -> (v / 255 - 0.5) / 0.5 in `dtype`, frame f at
- * out + f * frame_stride as [3][OH][OW] (channels_last = 0) or [OH][OW][3]; the uint8
- * values equal PIL's bit for bit.  Plans are device int arrays. */
+ * out + f * frame_stride as [3][OH][OW] (channels_last = 0) or [OH][OW][3] (channels_last =
+ * 1); the uint8 values equal PIL's bit for bit.  frame_stride is in elements of `dtype` and
+ * may exceed 3 * OH * OW: the elements between two frames are not written.  OH and OW are
+ * independent (PIL's resize to (OW, OH)); tmp is n * H * OW * 3 bytes of scratch.  Both
+ * layouts, a padded stride and OH != OW are tested against PIL, bit for bit
+ * (tests/test_gpu_guarded_data.py).  Plans are device int arrays. */
 int vd_resize_plan(int in_size, int out_size, int* bounds, int* coef, int ksize_cap);
 int vd_frames_resize_normalize(const uint8_t* frames, int64_t n, int H, int W, int OH, int OW,
                                const int* xbounds, const int* xcoef, int xksize,

@@ -18,6 +18,15 @@ inline int grid_for(int64_t work) {
   return (int)(g < cap ? (g > 0 ? g : 1) : cap);
 }
 
+// The one alignment rule of the per-sample kernels (scheduler math, guidance, DPM): the 8-wide
+// path needs whole vectors per sample and every non-null pointer 16-B aligned; anything else
+// runs one element at a time.
+inline bool cfg_vec8(int64_t per_sample, std::initializer_list<const void*> ptrs) {
+  uintptr_t a = 0;
+  for (const void* p : ptrs) a |= reinterpret_cast<uintptr_t>(p);
+  return per_sample % 8 == 0 && a % 16 == 0;
+}
+
 // ------------------------------------------------------------ timestep embedding
 // freqs: the caller's table (nullptr: computed here)
 __global__ void temb_kernel(const int64_t* __restrict__ t, int B, int dim, float log_max_period,
@@ -157,7 +166,7 @@ __device__ __forceinline__ void st_vec(T* p, const float (&v)[8], int n) {
   }
 }
 
-// Generic 3-in / 2-out per-sample op.  VEC = 8 when per_sample % 8 == 0.
+// Generic 3-in / 2-out per-sample op.  VEC = 8 under cfg_vec8's rule.
 template <typename T, typename Op, int VEC>
 __global__ void sched_kernel(Op op, const T* __restrict__ a, const T* __restrict__ b,
                              const T* __restrict__ c, T* __restrict__ o0, T* __restrict__ o1,
@@ -202,7 +211,7 @@ int launch_sched(Op op, const void* a, const void* b, const void* c, void* o0, v
   VD_REQUIRE(a && b && o0 && t, "null tensor argument");
   VD_REQUIRE(B > 0 && per_sample > 0, "empty tensor (B=%lld, per_sample=%lld)", (long long)B,
              (long long)per_sample);
-  const bool v8 = per_sample % 8 == 0;
+  const bool v8 = cfg_vec8(per_sample, {a, b, c, o0, o1});
   const int64_t work = B * per_sample / (v8 ? 8 : 1);
   return VD_DISPATCH_DTYPE(dtype, T, {
     if (v8)
@@ -531,13 +540,6 @@ __global__ void __launch_bounds__(kBlock) cfg_combine_kernel(
     gd.run(xc, xu, f, scale, g, VEC);
     st_vec(out + e, g, VEC);
   }
-}
-
-// 8-wide path: whole vectors per sample and every pointer 16-B aligned
-inline bool cfg_vec8(int64_t per_sample, std::initializer_list<const void*> ptrs) {
-  uintptr_t a = 0;
-  for (const void* p : ptrs) a |= reinterpret_cast<uintptr_t>(p);
-  return per_sample % 8 == 0 && a % 16 == 0;
 }
 
 // ------------------------------------------------------------ DPM-Solver++(2M) step
@@ -1102,7 +1104,7 @@ int vd_ddim_step_pred(const void* xt, const void* eps, const void* z, void* x_pr
   VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
              prediction);
   DDIMStep op{acp, t_prev, eta, clip, z != nullptr};
-  const bool v8 = per_sample % 8 == 0;
+  const bool v8 = cfg_vec8(per_sample, {xt, eps, z, x_prev, x0});
   const bool pv = prediction == VD_PRED_V;
   const int64_t work = B * per_sample / (v8 ? 8 : 1);
   return VD_DISPATCH_DTYPE(dtype, T, {

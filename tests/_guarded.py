@@ -18,8 +18,18 @@ attention buffer) is a view `.t` of given shape and strides into a flat payload 
 elements; the elements of the payload the view does not cover are the gaps.  They hold the
 pattern too: NaN under an input, and they must stay bit-intact under an output.
 
+Guarded.ranges lays several ragged ranges out in one flat payload -- range i occupies [starts[i],
+starts[i] + lengths[i]), everything between them is gap -- and exposes each range's pointer, so
+that a device descriptor table (vd_adam_desc, vd_ema_desc, vd_grad_desc) can point into it.
+Guarded.flat is one such range: a contiguous tensor that starts `off` elements into the payload,
+for a pointer that is element-aligned but not 16-byte aligned.  assert_finite is the value check
+by buffer and offset for operands the element-wise bounds do not cover.
+
 assert_clean(outputs, inputs) is the check after a call: every output fully written, its guards
-and gaps bit-intact; every input (guards, gaps and payload) bit-identical to its snapshot.
+and gaps bit-intact; every input (guards, gaps and payload) bit-identical to its snapshot.  A
+buffer that is both read and written (p, m, v, an EMA shadow, a clipped gradient, x0_hist, x_prev
+aliased to xt) goes into `inouts`: its guards and gaps must be bit-identical to the snapshot
+taken when it was frozen, and its payload is the value check's business.
 (fp32 arithmetic hands a NaN operand's payload on, so a pattern NaN read from an fp32 buffer that
 leaks into an fp32 output can arrive there bit for bit and is then reported as "unwritten"; in
 every other combination it fails the value check as a NaN.  Either way the call is red.)
@@ -30,8 +40,11 @@ GUARD = 1 << 20
 ALIGN = 256
 # quiet NaNs (exponent all ones, top mantissa bit set) with a recognisable payload; as the signed
 # integers the checks compare
-PATTERN = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FD5, torch.uint8: 0xFF}
-_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.uint8: torch.uint8}
+PATTERN = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FD5, torch.uint8: 0xFF,
+           # integer operands (timesteps, step counts, window tables): far outside every table
+           torch.int32: 0x7FC0DEAD, torch.int64: 0x7FC0DEAD7FC0DEAD}
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.uint8: torch.uint8,
+        torch.int32: torch.int32, torch.int64: torch.int64}
 
 
 class Guarded:
@@ -104,6 +117,61 @@ class Guarded:
                    nb * (n + pad_rows) * row, name)
 
     @classmethod
+    def ranges(cls, lengths, starts, dtype, device, data=None, name="buffer", span=None):
+        """A flat payload in which range i is [starts[i], starts[i] + lengths[i]) (elements, in
+        ascending order, not overlapping); the rest of the payload is gap.  .t is the whole flat
+        payload; .range(i) the view of range i, .range_ptr(i) its address.  `data`: one tensor per
+        range (the buffer is then frozen as an input), or None for pattern-filled ranges."""
+        lengths, starts = [int(n) for n in lengths], [int(s) for s in starts]
+        assert len(lengths) == len(starts) and all(n > 0 for n in lengths)
+        end = 0
+        for s_, n in zip(starts, lengths):
+            assert s_ >= end, "ranges overlap or are not ascending"
+            end = s_ + n
+        g = cls((end if span is None else int(span),), dtype, device, name=name)
+        assert g.span >= end
+        g.starts, g.lengths = starts, lengths
+        cover = torch.zeros(g.span, dtype=torch.bool)
+        for s_, n in zip(starts, lengths):
+            cover[s_:s_ + n] = True
+        g._cover = cover.to(device)
+        g._gap = ~g._cover if not bool(cover.all()) else None
+        if data is not None:
+            assert len(data) == len(lengths)
+            for i, d in enumerate(data):
+                g.range(i).copy_(d.reshape(-1))
+            g.freeze()
+        return g
+
+    @classmethod
+    def flat(cls, shape, dtype, device, data=None, off=0, name="buffer"):
+        """A contiguous tensor of `shape` that starts `off` elements into the payload (off = 1: a
+        pointer that is element-aligned but not 16-byte aligned; the elements before it are gap).
+        .p is its address and .value() its content, as fp32 on the CPU."""
+        shape = tuple(int(s) for s in shape)
+        n = 1
+        for s_ in shape:
+            n *= s_
+        g = cls.ranges([n], [off], dtype, device, None if data is None else [data], name=name)
+        g.p, g.logical = g.range_ptr(0), shape
+        return g
+
+    def value(self):
+        v = self.range_payloads()[0]
+        return (v.float() if v.is_floating_point() else v).reshape(self.logical)
+
+    def range(self, i):
+        return self.t[self.starts[i]:self.starts[i] + self.lengths[i]]
+
+    def range_ptr(self, i):
+        return self.ptr + self.starts[i] * self.t.element_size()
+
+    def range_payloads(self):
+        """Every range copied out to a CPU tensor."""
+        flat = self.t.detach().cpu()
+        return [flat[s_:s_ + n].clone() for s_, n in zip(self.starts, self.lengths)]
+
+    @classmethod
     def workspace(cls, nbytes, device, name="workspace"):
         """Exactly nbytes of 0xFF (stale NaN in every float format) inside intact guards."""
         return cls((int(nbytes),), torch.uint8, device, name=name)
@@ -126,8 +194,11 @@ class Guarded:
         return self._first_guard_fault() is None
 
     def unwritten(self):
-        """Mask, in the shape of .t, of the elements that still hold the pattern."""
-        return self._int == self._pat()
+        """Mask, in the shape of .t, of the elements that still hold the pattern (of a ranges
+        layout: the elements of the ranges; the gaps are the gap check's)."""
+        u = self._int == self._pat()
+        cover = getattr(self, "_cover", None)
+        return u if cover is None else u & cover
 
     def _first_gap_fault(self):
         if self._gap is None:
@@ -151,19 +222,38 @@ class Guarded:
     def unchanged(self):
         return self._first_change() is None
 
+    def _first_frame_change(self):
+        """As _first_change, for a buffer read and written in place: guards and gaps only."""
+        assert self._snap is not None, f"{self.name}: freeze() an in-place operand before the call"
+        bad = self.raw != self._snap
+        if self._gap is None:
+            bad[self.off:self.end] = False
+        else:
+            bad[self.off:self.end] &= self._gap
+        return int(bad.nonzero()[0]) - self.off if bool(bad.any()) else None
+
     def payload(self):
         """The view copied out to a contiguous CPU tensor of the buffer's dtype."""
         return self.t.detach().cpu().contiguous()
 
 
-def assert_clean(outputs=(), inputs=(), scratch=(), what=""):
+def assert_clean(outputs=(), inputs=(), scratch=(), what="", inouts=()):
     """After a call (synchronizes when a buffer lives on a GPU).  Outputs: guards intact, gaps
     intact, nothing unwritten.  Inputs: guards, gaps and payload bit-identical to the snapshot.
     Scratch (workspaces, whose content is the kernel's own business): guards intact.
+    Inouts (read and written in place; frozen before the call): guards and gaps bit-identical to
+    the snapshot, the payload left to the value check.
     The message names the buffer and the first offending offset, in elements from the start of
     the payload (negative: in the front guard)."""
-    if any(g.raw.is_cuda for g in tuple(outputs) + tuple(inputs) + tuple(scratch)):
+    every = tuple(outputs) + tuple(inputs) + tuple(scratch) + tuple(inouts)
+    if any(g.raw.is_cuda for g in every):
         torch.cuda.synchronize()
+    for g in inouts:
+        o = g._first_frame_change()
+        if o is not None:
+            where = "gap" if 0 <= o < g.span else "guard"
+            raise AssertionError(f"{what}: {g.name}: {where} written at payload offset {o} "
+                                 f"(payload is {g.span} elements)")
     for g in scratch:
         o = g._first_guard_fault()
         assert o is None, f"{what}: {g.name}: guard written at payload offset {o} " \
@@ -183,3 +273,20 @@ def assert_clean(outputs=(), inputs=(), scratch=(), what=""):
     for g in inputs:
         o = g._first_change()
         assert o is None, f"{what}: {g.name}: input modified at payload offset {o}"
+
+
+def assert_finite(buffers, what=""):
+    """The value check every guarded test ends with, by buffer and offset: no element of a
+    written buffer (of a ranges layout: of its ranges) is NaN or infinite.  A pattern NaN read
+    from a guard, a gap or a stale workspace slot that reached the buffer through arithmetic is
+    found here, whatever bits it arrived with."""
+    for g in buffers:
+        bad = ~torch.isfinite(g.t.float())
+        cover = getattr(g, "_cover", None)
+        if cover is not None:
+            bad &= cover
+        if bool(bad.any()):
+            idx = tuple(int(i) for i in bad.nonzero()[0])
+            o = sum(i * s for i, s in zip(idx, g.strides))
+            raise AssertionError(f"{what}: {g.name}: {int(bad.sum())} non-finite elements, first "
+                                 f"at {idx} (payload offset {o})")

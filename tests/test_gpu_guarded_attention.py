@@ -85,9 +85,11 @@ def _self_host(B, C, heads, T, HW, mode, seed, amp, legacy):
     return qkv, g, host
 
 
-def _self_run(B, C, heads, T, HW, mode, legacy, layout, dt, qkv, g, what):
+def _self_run(B, C, heads, T, HW, mode, legacy, layout, dt, qkv, g, what, no_ws=False):
     """The launches of AttentionFn.forward / .backward on guarded buffers; returns the logical
-    o [B, C, N], dqkv [B, 3C, N] (fp32, CPU) and lse in the reference's sequence order."""
+    o [B, C, N], dqkv [B, 3C, N] (fp32, CPU) and lse in the reference's sequence order.
+    no_ws: the forward is vd_attention_fwd, the form without a workspace, and the backward's
+    path predicate vd_attention_bwd_short_path is asserted on the guarded pointers."""
     from vdiff import _lib, ops
     lib = _lib.lib()
     N, row, orow, es = T * HW, 3 * C, C, 2 if dt == bf16 else 4
@@ -114,10 +116,14 @@ def _self_run(B, C, heads, T, HW, mode, legacy, layout, dt, qkv, g, what):
     LSE, WS = [], []
     for d, qo, ko, vo, oo in launches:
         lse = Guarded((d.nseq * d.seq_len,), f32, dev, name="lse")
-        nws = lib.vd_attention_fwd_workspace_size(d)
+        nws = 0 if no_ws else lib.vd_attention_fwd_workspace_size(d)
         ws = Guarded.workspace(nws, dev, "fwd workspace") if nws else None
-        _lib.call("vd_attention_fwd_ws", d, QKV.ptr + qo * es, QKV.ptr + ko * es,
-                  QKV.ptr + vo * es, O.ptr + oo * es, lse.ptr, ws and ws.ptr, nws, _st())
+        if no_ws:
+            _lib.call("vd_attention_fwd", d, QKV.ptr + qo * es, QKV.ptr + ko * es,
+                      QKV.ptr + vo * es, O.ptr + oo * es, lse.ptr, _st())
+        else:
+            _lib.call("vd_attention_fwd_ws", d, QKV.ptr + qo * es, QKV.ptr + ko * es,
+                      QKV.ptr + vo * es, O.ptr + oo * es, lse.ptr, ws and ws.ptr, nws, _st())
         LSE.append(lse)
         if ws is not None:
             WS.append(ws)
@@ -133,6 +139,14 @@ def _self_run(B, C, heads, T, HW, mode, legacy, layout, dt, qkv, g, what):
         q, k, v = (QKV.ptr + o_ * es for o_ in (qo, ko, vo))
         o, do = O.ptr + oo * es, DOUT.ptr + oo * es
         dq, dk, dv = (DQKV.ptr + o_ * es for o_ in (qo, ko, vo))
+        if no_ws:  # every guarded buffer is 16-B aligned: the shape alone decides; one
+            # element off in any one buffer sends the call to the flash kernels
+            assert lib.vd_attention_bwd_short_path(d, q, k, v, o, do, dq, dk, dv) == \
+                lib.vd_attention_short_path(d), what
+            ptrs = [q, k, v, o, do, dq, dk, dv]
+            for i in range(len(ptrs)):
+                off = ptrs[:i] + [ptrs[i] + es] + ptrs[i + 1:]
+                assert lib.vd_attention_bwd_short_path(d, *off) == 0, (what, i)
         if lib.vd_attention_bwd_short_path(d, q, k, v, o, do, dq, dk, dv):
             _lib.call("vd_attention_bwd", d, q, k, v, o, do, lse.ptr, dq, dk, dv, None, _st())
             continue
@@ -171,6 +185,37 @@ def test_guarded_self_attention(case, layout):
     got = dict(zip(("dq", "dk", "dv"), A.sequences(dqkv, C, T, HW, mode, heads, legacy)))
     got["o"], = A.sequences(o, C, T, HW, mode, heads, legacy)
     host.judge(got, lse, what, record_metric, test="guarded_attention", case=A.case_id(case),
+               layout=layout)
+
+
+def _no_ws_cases():
+    """Joint at every head_dim, spatial, temporal (flash and, T <= 32, the short kernels) and one
+    1157-token row (the hand-scheduled forward): cases of _self_cases, same tuples and seeds."""
+    cs = [(2, C, 1, 3, 67, "joint", 90 + C, 1.0, True, "auto") for C in (32, 64, 128, 256)]
+    cs += [(1, 64, 1, 1, 1157, "joint", 91 + 64, 1.0, True, "auto"),
+           (2, 64, 1, 5, 130, "spatial", 95, 1.0, True, "auto"),
+           (2, 64, 1, 40, 9, "temporal", 95, 1.0, True, "auto")]
+    cs += [(2, 64, 1, T, 37, "temporal", 600 + T, 1.0, True, "auto") for T in (9, 25)]
+    return [pytest.param(c, layout, id=A.case_id(c) + "-" + layout) for c in cs
+            for layout in (("exact",) if c[5] == "temporal" else ("exact", "padded"))]
+
+
+@pytest.mark.parametrize("case,layout", _no_ws_cases())
+def test_guarded_attention_fwd_without_workspace(case, layout):
+    """vd_attention_fwd, the entry point without a workspace, in place of vd_attention_fwd_ws, and
+    vd_attention_bwd_short_path on the guarded pointers (1 exactly for the short shapes, 0 as soon
+    as one buffer is an element off 16-byte alignment); the backward and the judgement are those
+    of test_guarded_self_attention."""
+    from vdiff import ops
+    B, C, heads, T, HW, mode, seed, amp, legacy, cfg = case
+    qkv, g, host = _self_host(B, C, heads, T, HW, mode, seed, amp, legacy)
+    what = f"guarded attention_fwd {A.case_id(case)} {layout}"
+    with ops.attention_config(cfg):
+        o, dqkv, lse = _self_run(B, C, heads, T, HW, mode, legacy, layout, bf16, qkv, g, what,
+                                 no_ws=True)
+    got = dict(zip(("dq", "dk", "dv"), A.sequences(dqkv, C, T, HW, mode, heads, legacy)))
+    got["o"], = A.sequences(o, C, T, HW, mode, heads, legacy)
+    host.judge(got, lse, what, record_metric, test="guarded_attention_fwd", case=A.case_id(case),
                layout=layout)
 
 

@@ -1,6 +1,8 @@
 """The conv entry points on guarded, NaN-poisoned buffers (tests/_guarded.py): vd_conv3d_fwd,
 vd_conv3d_bwd_data, vd_conv3d_bwd_weight_det and vd_channel_sums through vdiff._lib.call, with the
 operands, descriptors and call order of vdiff.ops.ConvFn, on buffers that are the test's own.
+The accumulating vd_conv3d_bwd_weight runs after the deterministic one, into a zeroed guarded
+[Cop][taps][Cip] buffer that is read and written in place, and is held to the same bound.
 
 Every operand (x, packed weights, bias, chan_add, residual, dy) lives between two 1 MiB guards of
 a NaN pattern, and so do y, dx and dw, which start out as the pattern; every workspace is exactly
@@ -159,6 +161,15 @@ def _run(kind, i, dt=torch.bfloat16, x_gap=0, y_cs=None, fwd_only=False, tag="")
     _lib.call("vd_conv3d_bwd_weight_det", db, X.ptr, DY.ptr, DW.ptr, Co, Ci, WS.ptr, nws, st)
     assert_clean([DW], [X, DY], [WS], what=what + " bwd_weight_det")
     rdw = assert_elementwise(DW.payload(), dw, dwm, n_dw, False, what=what + " dw")
+    # the accumulating form (ConvFn's split-K A/B path): dw [Cop][taps][Cip] fp32, zeroed by the
+    # caller, read and written in place; any summation order lies inside the same bound
+    DWA = Guarded((Cop, taps, Cip), torch.float32, dev, torch.zeros(Cop, taps, Cip), name="dw +=")
+    _lib.call("vd_conv3d_bwd_weight", db, X.ptr, DY.ptr, DWA.ptr, st)
+    assert_clean([], [X, DY], what=what + " bwd_weight", inouts=[DWA])
+    acc = DWA.payload()
+    assert not bool(acc[Co:].any()) and not bool(acc[:, :, Ci:].any()), what + " dw += padding"
+    assert_elementwise(acc[:Co, :, :Ci].permute(0, 2, 1).reshape(dw.shape), dw, dwm, n_dw, False,
+                       what=what + " dw +=")
     print(f"guarded conv {what}: err/bound y {ry:.3f} dx {rdx:.3f} dw {rdw:.3f}")
     record_metric(test="guarded_conv", tag=tag, kind=kind, case=i, fp32=not bf, x_cs=x_cs,
                   y_cs=y_cs, y=ry, dx=rdx, dw=rdw)

@@ -3,7 +3,7 @@ CPU tensors and must be reported, and an honest "kernel" must pass."""
 import pytest
 import torch
 
-from _guarded import ALIGN, GUARD, PATTERN, Guarded, assert_clean
+from _guarded import ALIGN, GUARD, PATTERN, Guarded, assert_clean, assert_finite
 
 DTYPES = [torch.float32, torch.bfloat16]
 
@@ -143,3 +143,112 @@ def test_no_nan_free_value_equals_the_pattern():
     nan32 = (torch.tensor([float("inf")]) - torch.tensor([float("inf")])).view(torch.int32)
     assert int(nan32) & 0x7FFFFFFF != p
     assert int(nan32.view(torch.float32).bfloat16().view(torch.int16)) & 0x7FFF != q
+
+
+# ------------------------------------------------------------------ ragged ranges in one payload
+LENGTHS = [1, 7, 8, 9, 17, 2049]
+STARTS = [0, 8, 16, 32, 49, 80]      # 49: 4-byte but not 16-byte aligned in fp32
+
+
+def _range_pair(dtype):
+    """Ranged input src, ranged in-place operand dst (a shadow, a moment), ranged output out."""
+    g = torch.Generator().manual_seed(3)
+    data = [torch.randn(n, generator=g) for n in LENGTHS]
+    src = Guarded.ranges(LENGTHS, STARTS, dtype, "cpu", data, name="src")
+    dst = Guarded.ranges(LENGTHS, STARTS, dtype, "cpu", [d * 0.5 for d in data], name="dst")
+    out = Guarded.ranges(LENGTHS, STARTS, dtype, "cpu", name="out")
+    return src, dst, out
+
+
+def _honest_ranges(src, dst, out):
+    for i in range(len(LENGTHS)):
+        dst.range(i).add_(src.range(i))
+        out.range(i).copy_(src.range(i) * 2)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_ranges_layout_and_honest_kernel(dtype):
+    src, dst, out = _range_pair(dtype)
+    es = _es(dtype)
+    assert src.span == STARTS[-1] + LENGTHS[-1]
+    for i, (s, n) in enumerate(zip(STARTS, LENGTHS)):
+        assert src.range_ptr(i) == src.ptr + s * es == src.range(i).data_ptr()
+        assert src.range(i).numel() == n
+    assert src.range_ptr(4) % es == 0 and src.range_ptr(4) % 16 != 0
+    gaps = sorted(set(range(src.span)) - {s + k for s, n in zip(STARTS, LENGTHS) for k in range(n)})
+    assert gaps and bool(torch.isnan(src.t[gaps].float()).all())      # NaN under an input
+    assert int(out.unwritten().sum()) == sum(LENGTHS)                 # the gaps are not counted
+    assert not bool(src.unwritten().any())
+    _honest_ranges(src, dst, out)
+    assert_clean(outputs=[out], inputs=[src], inouts=[dst], what="honest ranges")
+    assert_finite([out, dst], what="honest ranges")
+    for a, b in zip(out.range_payloads(), src.range_payloads()):
+        assert torch.equal(a, b * 2)
+    # an in-place operand has to be frozen before the call, like an input
+    fresh = Guarded.ranges(LENGTHS, STARTS, dtype, "cpu", name="fresh")
+    with pytest.raises(AssertionError, match="freeze"):
+        assert_clean(inouts=[fresh], what="unfrozen")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("back", [1, 7])
+def test_wide_tail_store_into_the_gap_is_reported(dtype, back):
+    """An 8-element store that starts `back` elements before the end of a range (the vector body
+    run one vector too far) and so writes 8 - back elements of the gap behind it: reported on an
+    output and on an in-place operand, by buffer and by the offset of the first gap element."""
+    src, dst, out = _range_pair(dtype)
+    _honest_ranges(src, dst, out)
+    i = 3                                            # [32, 41): 8 gap elements follow it
+    at = STARTS[i] + LENGTHS[i] - back
+    for buf in (out, dst):
+        buf.t[at:at + 8] = 1.0
+    first = STARTS[i] + LENGTHS[i]
+    with pytest.raises(AssertionError, match=f"out: gap written at payload offset {first}$"):
+        assert_clean(outputs=[out], inputs=[src], what="planted")
+    with pytest.raises(AssertionError, match=rf"dst: gap written at payload offset {first} "):
+        assert_clean(inputs=[src], inouts=[dst], what="planted")
+    # past the last range the same store runs into the back guard
+    src, dst, out = _range_pair(dtype)
+    _honest_ranges(src, dst, out)
+    at = dst.span - back
+    dst.raw.view(dtype)[dst.off + at:dst.off + at + 8] = 1.0
+    with pytest.raises(AssertionError, match=rf"dst: guard written at payload offset {dst.span} "):
+        assert_clean(inputs=[src], inouts=[dst], what="planted")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_gap_read_that_reaches_an_output_is_reported(dtype):
+    """A vector body that reads 8 elements from the last element of a source range on: the gap's
+    NaN enters the arithmetic and arrives in the output and in the in-place operand.  Nothing was
+    written out of place, so the layout check alone may pass; the value check names the buffer
+    and the offset."""
+    src, dst, out = _range_pair(dtype)
+    _honest_ranges(src, dst, out)
+    i = 2                                            # [16, 24), then 8 gap elements
+    s, n = STARTS[i], LENGTHS[i]
+    leak = src.t[s + n - 1:s + n + 7].float().sum()  # one element of the range, seven of the gap
+    assert bool(torch.isnan(leak))
+    out.range(i)[n - 1] = leak
+    dst.range(i)[n - 1] += leak
+    assert src.unchanged() and out.gaps_intact() and out.guards_intact()
+    with pytest.raises(AssertionError,
+                       match=rf"out: 1 non-finite elements, first at \({s + n - 1},\) "
+                             rf"\(payload offset {s + n - 1}\)"):
+        assert_finite([out], what="planted")
+    with pytest.raises(AssertionError, match=rf"dst: 1 non-finite elements, first at "
+                                             rf"\({s + n - 1},\)"):
+        assert_finite([dst], what="planted")
+    # the gaps themselves are NaN and are not the value check's business
+    assert_finite([src], what="gaps")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_unwritten_range_is_reported(dtype):
+    src, dst, out = _range_pair(dtype)
+    for i in range(len(LENGTHS)):
+        if i != 4:                                   # the 17 elements at 49 are skipped
+            out.range(i).copy_(src.range(i) * 2)
+    with pytest.raises(AssertionError,
+                       match=rf"out: 17 of {out.span} elements unwritten, first at \(49,\) "
+                             r"\(payload offset 49\)"):
+        assert_clean(outputs=[out], inputs=[src], what="planted")
