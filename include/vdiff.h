@@ -63,7 +63,8 @@ int vd_timestep_embedding_tab(const int64_t* t, int B, int dim, const float* fre
  *
  * Alignment of the per-sample kernels -- ONE rule for every entry point of this group:
  * vd_q_sample, vd_p_sample_v1 / _v2 / _cosine, vd_ddim_step / _pred, vd_cfg_stats,
- * vd_cfg_combine, vd_ddim_step_cfg / _cfg_pred, vd_dpm_step / _cfg.  A call moves 8 elements
+ * vd_cfg_combine, vd_ddim_step_cfg / _cfg_pred, vd_dpm_step / _cfg, vd_x0_abs_quantile,
+ * vd_ddim_step_thr, vd_dpm_step_thr.  A call moves 8 elements
  * per lane (16-byte accesses) when per_sample % 8 == 0 AND every non-null tensor pointer it is
  * given (inputs, outputs, the duplicate, the history) is 16-byte aligned; any other call runs
  * one element at a time, so element-aligned pointers are always legal.  Both paths perform the
@@ -238,6 +239,78 @@ int vd_dpm_step_cfg(const void* xt, const void* eps_c, const void* eps_u, void* 
                     void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
                     const int64_t* step, float w, float rescale, const void* workspace,
                     int clip, int64_t B, int64_t per_sample, int dtype, void* stream);
+
+/* ---- dynamic thresholding (Saharia et al. 2022, section 2.3; build extension, no reference
+ * counterpart: the reference's samplers clamp x0 to [-1, 1]) ----
+ * Per sample b over its P = per_sample elements, with x0 in fp32 as the step kernel forms it:
+ *   q_b  = the rank-th smallest |x0_i| (0-based; an element of the data, never interpolated:
+ *          torch.quantile(..., interpolation="higher") with rank = ceil(p (P - 1)));
+ *   s_b  = min(max(q_b, floor), cap)               (sampling: floor = 1, cap = threshold_max);
+ *   x0_i = clamp(x0_i, -s_b, s_b) / s_b            (vd_ddim_step_thr / vd_dpm_step_thr).
+ * The order is that of the unsigned bit patterns of |x0|: a NaN sorts above +inf, and a NaN q_b
+ * becomes the floor (fmaxf).  The rank is the host's: the library never sees p.
+ *
+ * vd_x0_source says where x0 comes from; it is formed again in every pass and never written:
+ *   VD_X0_IDENTITY  x0 = x (eps, eps_u NULL);
+ *   VD_X0_DDIM      vd_ddim_step_pred's x0 from x = xt, eps (the model's eps or v, `prediction`),
+ *                   t int64[B] and acp;
+ *   VD_X0_DPM       vd_dpm_step's x0 from x = xt, eps, coef [n_steps][8] and the device scalar
+ *                   `step`, clamped into [0, n_steps - 1] as the step kernel clamps it.
+ * eps_u != NULL (the two step rules): eps is eps_c and the model output is guided first, f_b
+ * (eps_u + w (eps_c - eps_u)), with rescale > 0 from the vd_cfg_stats workspace `cfg_workspace`
+ * (NULL allowed when rescale == 0), exactly as vd_ddim_step_cfg_pred / vd_dpm_step_cfg guide it.
+ * Fields a rule does not read are ignored.
+ *
+ * vd_x0_abs_quantile writes s fp32 [B] (every entry).  Method: a most-significant-digit radix
+ * select on the bit pattern of |x0|, four 8-bit digits, EIGHT launches: per digit one histogram
+ * launch (block k of sample b counts its fixed range into LDS with integer atomics and stores
+ * its row to the workspace with plain stores) and one scan launch (one block per sample adds the
+ * rows, finds the bin that holds the rank, hands prefix and remaining rank to the next digit;
+ * the last one writes s).  All histogram launches are one kernel, so every pass sees the same
+ * bits of x0.  No global atomics, no float atomics, no memset, no cross-block communication
+ * inside a launch, and every workspace word read was written earlier in the same call: the
+ * workspace (vd_x0_quantile_workspace_size bytes, 4-byte aligned) may be uninitialised, and the
+ * bits are the same eager and replayed from a HIP graph.  B <= 65535, per_sample < 2^32, 0 <=
+ * rank < per_sample, cap >= floor.  Tensors follow the alignment rule above (x, eps, eps_u).
+ *
+ * vd_ddim_step_thr: vd_ddim_step_cfg_pred with x0 = clamp(x0, -s_b, s_b) / s_b, s_b = thresh[b]
+ * (device fp32 [B], >= 1) in place of the static clamp; x_prev, x_prev_dup and x0 are formed
+ * from the thresholded x0, the direction term keeps the model's own (guided) eps.  eps_u == NULL:
+ * the unguided step on eps_c (w, rescale and workspace are then not read).  Overwrites x_prev,
+ * x_prev_dup and x0 (each of the last two may be NULL); x_prev may alias xt; z may be NULL when
+ * eta == 0.
+ * vd_dpm_step_thr: vd_dpm_step_cfg the same way: x_prev, x_prev_dup (may be NULL) and the
+ * history x0_hist (in place, never NULL) get the thresholded x0; eps_u == NULL is vd_dpm_step's
+ * unguided update. */
+enum vd_x0_rule { VD_X0_IDENTITY = 0, VD_X0_DDIM = 1, VD_X0_DPM = 2 };
+typedef struct {            /* 88 bytes */
+  const void* x;            /* the data (identity) or xt */
+  const void* eps;          /* the model's output; eps_c when eps_u is given */
+  const void* eps_u;        /* NULL: unguided */
+  const int64_t* t;         /* DDIM */
+  const float* acp;         /* DDIM */
+  const float* coef;        /* DPM */
+  const int64_t* step;      /* DPM */
+  const void* cfg_workspace;
+  int64_t n_steps;          /* DPM */
+  int32_t rule;             /* enum vd_x0_rule */
+  int32_t prediction;       /* DDIM: enum vd_prediction */
+  float w;
+  float rescale;
+} vd_x0_source;
+size_t vd_x0_quantile_workspace_size(int64_t B, int64_t per_sample);
+int vd_x0_abs_quantile(const vd_x0_source* src, int64_t rank, float floor, float cap, int64_t B,
+                       int64_t per_sample, int dtype, float* s, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int vd_ddim_step_thr(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                     void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                     const int64_t* t_prev, const float* acp, float w, float rescale,
+                     const void* workspace, float eta, int prediction, const float* thresh,
+                     int64_t B, int64_t per_sample, int dtype, void* stream);
+int vd_dpm_step_thr(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
+                    void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
+                    const int64_t* step, float w, float rescale, const void* workspace,
+                    const float* thresh, int64_t B, int64_t per_sample, int dtype, void* stream);
 
 /* Long-clip sampling (build extension, no reference counterpart): a latent of L frames is
  * denoised as W overlapping windows of T frames, one batched forward per step, and the windows'

@@ -119,9 +119,12 @@ struct DDIMStep {
   // PRED_V: `eps` holds the model's v (Salimans & Ho 2022): x0 = sqrt(a_t) xt - sqrt(1 - a_t) v,
   // eps = sqrt(1 - a_t) xt + sqrt(a_t) v; clip, direction and noise terms are the same.  The
   // eps instantiation is the code it was before the template parameter: the same bits.
-  template <bool PRED_V>
+  // THR (dynamic thresholding, vd_ddim_step_thr): x0 = clamp(x0, -s, s) / s with the sample's
+  // s = thr[b] >= 1 of vd_x0_abs_quantile; the direction term keeps the model's own eps, as
+  // clip does.  THR = false is the code it was before this parameter too.
+  template <bool PRED_V, bool THR = false>
   __device__ void run(int64_t tb, int64_t tp, const float* xt, const float* eps, const float* z,
-                      float* xprev, float* x0o, int n) const {
+                      float* xprev, float* x0o, int n, float s = 1.f) const {
     const float at = acp[tb];
     const float ap = tp >= 0 ? acp[tp] : 1.f;
     const float sq_at = sqrtf(at), sq_1mat = sqrtf(1.f - at);
@@ -133,6 +136,7 @@ struct DDIMStep {
         float x0 = sq_at * xt[i] - sq_1mat * eps[i];
         const float e = sq_1mat * xt[i] + sq_at * eps[i];
         if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+        if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
         x0o[i] = x0;
         float v = sq_ap * x0 + dir * e;
         if (has_z) v += sigma * z[i];
@@ -140,6 +144,7 @@ struct DDIMStep {
       } else {
         float x0 = (xt[i] - sq_1mat * eps[i]) / sq_at;
         if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+        if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
         x0o[i] = x0;
         float v = sq_ap * x0 + dir * eps[i];
         if (has_z) v += sigma * z[i];
@@ -562,12 +567,17 @@ struct DPMStep {
     const float* r = coef + s * 8;
     return Row{r[0], r[1], r[2], r[3], r[4]};
   }
-  // x_prev is formed from the fp32 x0, not from the value a bf16 history rounds it to
+  // x_prev is formed from the fp32 x0, not from the value a bf16 history rounds it to.
+  // THR: the thresholded x0 of DDIMStep::run (vd_dpm_step_thr); it is what x_prev and the
+  // history get.
+  template <bool THR = false>
   __device__ __forceinline__ void run(const Row& r, bool hist, const float* xt, const float* eps,
-                                      const float* last, float* xprev, float* x0o, int n) const {
+                                      const float* last, float* xprev, float* x0o, int n,
+                                      float s = 1.f) const {
     for (int i = 0; i < n; ++i) {
       float x0 = (xt[i] - r.sigma * eps[i]) / r.alpha;
       if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+      if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
       x0o[i] = x0;
       float v = r.A * xt[i] + r.B * x0;
       if (hist) v += r.C * last[i];
@@ -631,6 +641,240 @@ __global__ void __launch_bounds__(kBlock) cfg_dpm_kernel(
 
 inline dim3 cfg_grid(int64_t per_sample, int vec, int64_t B) {
   return dim3((unsigned)grid_for(per_sample / vec), (unsigned)B);
+}
+
+// ------------------------------------------------------------ dynamic thresholding
+// s_b = min(max(q_b, floor), cap), q_b the rank-th smallest |x0| of sample b (0-based; an element
+// of the data): Imagen's dynamic threshold (Saharia et al. 2022, section 2.3) with the "higher"
+// order statistic.  x0 is never written to memory: every pass forms it again from the step's
+// inputs with the step kernels' own code -- DDIMStep::run / DPMStep::run without the clamp, after
+// CfgGuide::run and cfg_factor -- so it has the bits the thresholded step sees.
+//
+// Method: a most-significant-digit radix select over the bit pattern of |x0| (non-negative
+// floats order as their uint32 patterns; a NaN sorts above +inf), four 8-bit digits, EIGHT
+// launches: per digit one histogram launch and one scan launch.
+//   histogram: block k of sample b counts the digit of the elements of its fixed range
+//     (cfg_chunk's ranges) whose higher digits equal the prefix found so far, into LDS (integer
+//     atomics: a count does not depend on the order) and stores its row ws[b][k][256] with plain
+//     stores.  kThrCopies sub-histograms per block, picked by the lane: the first digit is the
+//     sign and seven exponent bits, so a wave's lanes meet in two or three bins, and same-address
+//     LDS atomics serialise.
+//   scan: one block per sample adds the rows (integer adds: any order gives the same counts),
+//     finds the bin that holds the rank and writes prefix and remaining rank to the sample's
+//     state words; the last scan writes s[b].
+// All four histogram launches are ONE kernel instantiation with the shift as an argument: the
+// same machine code forms x0, so every pass sees the same bits whatever the compiler contracts.
+// No global atomics, no float atomics, no memset, no cross-block communication inside a launch;
+// every workspace word that is read was written earlier in the same call.
+constexpr int kThrBins = 256;
+constexpr int kThrCopies = 16;
+constexpr int kThrState = 4;  // uint32 per sample: prefix, remaining rank, 2 unused
+static_assert(kThrBins == kBlock, "x0_hist_kernel: thread d stores bin d");
+
+// Device view of vd_x0_source (include/vdiff.h).  u == nullptr: unguided.
+struct X0Source {
+  int rule;
+  bool pred_v;
+  DDIMStep ddim;
+  const int64_t* t;
+  DPMStep dpm;
+  CfgGuide gd;
+  const float* part;
+  int nb_cfg;
+  float phi;
+};
+
+inline size_t thr_state_offset(int64_t B, int nb) { return (size_t)B * nb * kThrBins; }
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kBlock) x0_hist_kernel(
+    X0Source src, const T* __restrict__ x, const T* __restrict__ c, const T* __restrict__ u,
+    int64_t P, int64_t chunk, int shift, uint32_t* __restrict__ ws, const uint32_t* state) {
+  __shared__ uint32_t hist[kThrBins * kThrCopies];
+  const int nb = gridDim.x;
+  const int64_t b = blockIdx.y;
+  const bool guided = u != nullptr;
+  const bool scale = guided && src.phi > 0.f;
+  const float f = scale ? cfg_factor(src.part, b, src.nb_cfg, src.phi) : 1.f;
+  // the digits above this one, found by the earlier scans (none before the first pass)
+  const bool first = shift == 24;
+  const uint32_t prefix = first ? 0u : state[b * kThrState];
+  const int hi = first ? 0 : shift + 8;
+  for (int i = threadIdx.x; i < kThrBins * kThrCopies; i += kBlock) hist[i] = 0u;
+  __syncthreads();
+  int64_t tb = 0;
+  DPMStep::Row r{};
+  if (src.rule == VD_X0_DDIM) tb = src.t[b];
+  if (src.rule == VD_X0_DPM) r = src.dpm.row();
+  const int64_t lo = (int64_t)blockIdx.x * chunk;
+  const int64_t end = lo + chunk < P ? lo + chunk : P;
+  const int64_t base = b * P;
+  const int copy = threadIdx.x & (kThrCopies - 1);
+  for (int64_t i = lo + (int64_t)threadIdx.x * VEC; i < end; i += (int64_t)kBlock * VEC) {
+    const int64_t e = base + i;
+    float xa[8], x0[8];
+    ld_vec(x + e, xa, VEC);
+    if (src.rule == VD_X0_IDENTITY) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) x0[k] = xa[k];
+    } else {
+      float xc[8], g[8], xz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, y0[8];
+      ld_vec(c + e, xc, VEC);
+      if (guided) {
+        float xu[8];
+        ld_vec(u + e, xu, VEC);
+        src.gd.run(xc, xu, f, scale, g, VEC);
+      } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) g[k] = xc[k];
+      }
+      if (src.rule == VD_X0_DPM)
+        src.dpm.run(r, false, xa, g, xz, y0, x0, VEC);
+      else if (src.pred_v)
+        src.ddim.run<true>(tb, -1, xa, g, xz, y0, x0, VEC);
+      else
+        src.ddim.run<false>(tb, -1, xa, g, xz, y0, x0, VEC);
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      const uint32_t bits = __float_as_uint(x0[k]) & 0x7fffffffu;
+      if (first || (bits >> hi) == prefix)
+        atomicAdd(&hist[((bits >> shift) & (kThrBins - 1)) * kThrCopies + copy], 1u);
+    }
+  }
+  __syncthreads();
+  // thread d adds bin d's copies, starting at its own: the lanes of a wave read different banks
+  uint32_t n = 0;
+#pragma unroll
+  for (int j = 0; j < kThrCopies; ++j)
+    n += hist[threadIdx.x * kThrCopies + ((j + threadIdx.x) & (kThrCopies - 1))];
+  ws[(b * nb + blockIdx.x) * kThrBins + threadIdx.x] = n;
+}
+
+// kThrScanParts groups of kThrBins threads: group j adds rows j, j + kThrScanParts, ... of its
+// bin (a single block per sample walks up to 128 rows, and its time is the latency of those
+// loads: four independent streams, each unrolled, in place of one cut a scan from 19 to
+// a few microseconds), then group 0 adds the groups' sums and scans the bins.
+constexpr int kThrScanParts = 4;
+
+__global__ void __launch_bounds__(kThrBins* kThrScanParts)
+    x0_scan_kernel(const uint32_t* __restrict__ ws, int nb, int shift, uint32_t rank, float floor_,
+                   float cap, uint32_t* state, float* __restrict__ s_out) {
+  __shared__ uint32_t part[kThrScanParts][kThrBins];
+  __shared__ uint32_t cum[kThrBins];
+  const int64_t b = blockIdx.x;
+  const int d = threadIdx.x & (kThrBins - 1);
+  const int grp = threadIdx.x / kThrBins;
+  const bool first = shift == 24;
+  const uint32_t prefix = first ? 0u : state[b * kThrState];
+  const uint32_t want = first ? rank : state[b * kThrState + 1];
+  const uint32_t* rows = ws + b * nb * kThrBins;
+  uint32_t n = 0;
+#pragma unroll 8
+  for (int k = grp; k < nb; k += kThrScanParts) n += rows[k * kThrBins + d];
+  part[grp][d] = n;
+  __syncthreads();  // also: every thread has read the state words before one is rewritten
+  if (grp == 0) {
+#pragma unroll
+    for (int j = 1; j < kThrScanParts; ++j) n += part[j][d];
+    cum[d] = n;
+  }
+  __syncthreads();
+  // inclusive scan over the bins (Hillis-Steele; integer adds, any order gives the same counts)
+  for (int off = 1; off < kThrBins; off <<= 1) {
+    const uint32_t add = (grp == 0 && d >= off) ? cum[d - off] : 0u;
+    __syncthreads();
+    if (grp == 0) cum[d] += add;
+    __syncthreads();
+  }
+  if (grp != 0) return;
+  const uint32_t incl = cum[d], excl = incl - n;
+  // the counts are those of the elements under `prefix`, more than `want` of them: one bin
+  if (want >= excl && want < incl) {
+    const uint32_t found = (prefix << 8) | (uint32_t)d;
+    if (shift == 0) {
+      // fmaxf: a NaN quantile becomes the floor
+      s_out[b] = fminf(fmaxf(__uint_as_float(found), floor_), cap);
+    } else {
+      state[b * kThrState] = found;
+      state[b * kThrState + 1] = want - excl;
+    }
+  }
+}
+
+// Guide (u != nullptr) + rescale + the thresholded DDIM step: cfg_ddim_kernel's layout
+// (blockIdx.y = sample, x_prev may alias xt, xdup gets x_prev's values) with s = thr[b].
+template <typename T, int VEC, bool PRED_V>
+__global__ void __launch_bounds__(kBlock) thr_ddim_kernel(
+    DDIMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
+    const T* __restrict__ z, T* xprev, T* xdup, T* __restrict__ x0,
+    const int64_t* __restrict__ t, const float* __restrict__ part, int nb, float phi,
+    const float* __restrict__ thr, int64_t per_sample) {
+  const int64_t b = blockIdx.y;
+  const bool guided = u != nullptr;
+  const bool scale = guided && phi > 0.f;
+  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
+  const float s = thr[b];
+  const int64_t tb = t[b], tp = op.tprev[b];
+  const int64_t base = b * per_sample;
+  const int64_t nvec = per_sample / VEC;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = base + v * VEC;
+    float xa[8], xc[8], xz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
+    ld_vec(xt + e, xa, VEC);
+    ld_vec(c + e, xc, VEC);
+    if (guided) {
+      float xu[8];
+      ld_vec(u + e, xu, VEC);
+      gd.run(xc, xu, f, scale, g, VEC);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) g[k] = xc[k];
+    }
+    if (z) ld_vec(z + e, xz, VEC);
+    op.run<PRED_V, true>(tb, tp, xa, g, xz, y0, y1, VEC, s);
+    st_vec(xprev + e, y0, VEC);
+    if (xdup) st_vec(xdup + e, y0, VEC);
+    if (x0) st_vec(x0 + e, y1, VEC);
+  }
+}
+
+// The same for the DPM-Solver++(2M) step: cfg_dpm_kernel's layout and aliasing rules.
+template <typename T, int VEC>
+__global__ void __launch_bounds__(kBlock) thr_dpm_kernel(
+    DPMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
+    T* xprev, T* xdup, T* hist, const float* __restrict__ part, int nb, float phi,
+    const float* __restrict__ thr, int64_t per_sample) {
+  const int64_t b = blockIdx.y;
+  const bool guided = u != nullptr;
+  const bool scale = guided && phi > 0.f;
+  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
+  const float s = thr[b];
+  const DPMStep::Row r = op.row();
+  const bool use_hist = r.C != 0.f;
+  const int64_t base = b * per_sample;
+  const int64_t nvec = per_sample / VEC;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = base + v * VEC;
+    float xa[8], xc[8], xh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
+    ld_vec(xt + e, xa, VEC);
+    ld_vec(c + e, xc, VEC);
+    if (guided) {
+      float xu[8];
+      ld_vec(u + e, xu, VEC);
+      gd.run(xc, xu, f, scale, g, VEC);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) g[k] = xc[k];
+    }
+    if (use_hist) ld_vec(hist + e, xh, VEC);
+    op.run<true>(r, use_hist, xa, g, xh, y0, y1, VEC, s);
+    st_vec(xprev + e, y0, VEC);
+    if (xdup) st_vec(xdup + e, y0, VEC);
+    st_vec(hist + e, y1, VEC);
+  }
 }
 
 }  // namespace
@@ -1256,6 +1500,147 @@ int vd_dpm_step_cfg(const void* xt, const void* eps_c, const void* eps_u, void* 
       cfg_dpm_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
           op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
           (T*)x0_hist, part, nb, rescale, per_sample);
+  });
+}
+
+size_t vd_x0_quantile_workspace_size(int64_t B, int64_t per_sample) {
+  if (B <= 0 || per_sample <= 0) return 0;
+  return (thr_state_offset(B, cfg_blocks(per_sample)) + (size_t)B * kThrState) * sizeof(uint32_t);
+}
+
+int vd_x0_abs_quantile(const vd_x0_source* src, int64_t rank, float floor, float cap, int64_t B,
+                       int64_t per_sample, int dtype, float* s, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  VD_REQUIRE(src && s && workspace, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && per_sample <= (int64_t)0xffffffffll,
+             "bad shape (B=%lld, per_sample=%lld)", (long long)B, (long long)per_sample);
+  VD_REQUIRE(rank >= 0 && rank < per_sample, "rank %lld outside [0, per_sample = %lld)",
+             (long long)rank, (long long)per_sample);
+  VD_REQUIRE(cap >= floor, "cap %g below floor %g", (double)cap, (double)floor);
+  VD_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, "workspace must be 4-B aligned");
+  VD_REQUIRE(workspace_bytes >= vd_x0_quantile_workspace_size(B, per_sample),
+             "workspace too small");
+  VD_REQUIRE(src->x, "null source tensor");
+  X0Source xs = {};
+  xs.rule = src->rule;
+  if (src->rule == VD_X0_IDENTITY) {
+    VD_REQUIRE(!src->eps && !src->eps_u, "the identity source reads x alone");
+  } else if (src->rule == VD_X0_DDIM) {
+    VD_REQUIRE(src->eps && src->t && src->acp, "DDIM source: null eps, t or acp");
+    VD_REQUIRE(src->prediction == VD_PRED_EPS || src->prediction == VD_PRED_V,
+               "unknown prediction type %d", src->prediction);
+    xs.pred_v = src->prediction == VD_PRED_V;
+    xs.ddim = DDIMStep{src->acp, nullptr, 0.f, 0, 0};
+    xs.t = src->t;
+  } else if (src->rule == VD_X0_DPM) {
+    VD_REQUIRE(src->eps && src->coef && src->step && src->n_steps > 0,
+               "DPM source: null eps, coef or step, or an empty table");
+    xs.dpm = DPMStep{src->coef, src->n_steps, src->step, 0};
+  } else {
+    return vd::fail(VD_EINVAL, "unknown x0 rule %d", src->rule);
+  }
+  if (src->eps_u) {
+    VD_REQUIRE(src->rescale >= 0.f && src->rescale <= 1.f, "rescale %g outside [0, 1]",
+               (double)src->rescale);
+    VD_REQUIRE(src->rescale == 0.f || src->cfg_workspace,
+               "rescale > 0 needs the vd_cfg_stats workspace (null)");
+    xs.gd = CfgGuide{src->w};
+    xs.part = static_cast<const float*>(src->cfg_workspace);
+    xs.nb_cfg = cfg_blocks(per_sample);
+    xs.phi = src->rescale;
+  }
+  const int nb = cfg_blocks(per_sample);
+  const int64_t chunk = cfg_chunk(per_sample, nb);
+  const dim3 grid((unsigned)nb, (unsigned)B);
+  uint32_t* rows = static_cast<uint32_t*>(workspace);
+  uint32_t* state = rows + thr_state_offset(B, nb);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {src->x, src->eps, src->eps_u});
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    const T* x = (const T*)src->x;
+    const T* c = (const T*)src->eps;
+    const T* u = (const T*)src->eps_u;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      if (v8)
+        x0_hist_kernel<T, 8><<<grid, kBlock, 0, st>>>(xs, x, c, u, per_sample, chunk, shift, rows,
+                                                      state);
+      else
+        x0_hist_kernel<T, 1><<<grid, kBlock, 0, st>>>(xs, x, c, u, per_sample, chunk, shift, rows,
+                                                      state);
+      x0_scan_kernel<<<(unsigned)B, kThrBins * kThrScanParts, 0, st>>>(
+          rows, nb, shift, (uint32_t)rank, floor, cap, state, s);
+    }
+  });
+}
+
+int vd_ddim_step_thr(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                     void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                     const int64_t* t_prev, const float* acp, float w, float rescale,
+                     const void* workspace, float eta, int prediction, const float* thresh,
+                     int64_t B, int64_t per_sample, int dtype, void* stream) {
+  VD_REQUIRE(xt && eps_c && x_prev && t && t_prev && acp && thresh, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
+             (long long)B, (long long)per_sample);
+  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
+  VD_REQUIRE(!eps_u || rescale == 0.f || workspace,
+             "rescale > 0 needs the vd_cfg_stats workspace (null)");
+  VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
+  VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
+             prediction);
+  DDIMStep op{acp, t_prev, eta, 0, z != nullptr};
+  const CfgGuide gd{w};
+  const int nb = cfg_blocks(per_sample);
+  const float* part = static_cast<const float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0});
+  const bool pv = prediction == VD_PRED_V;
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (v8 && !pv)
+      thr_ddim_kernel<T, 8, false><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
+    else if (!pv)
+      thr_ddim_kernel<T, 1, false><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
+    else if (v8)
+      thr_ddim_kernel<T, 8, true><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
+    else
+      thr_ddim_kernel<T, 1, true><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
+          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
+  });
+}
+
+int vd_dpm_step_thr(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
+                    void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
+                    const int64_t* step, float w, float rescale, const void* workspace,
+                    const float* thresh, int64_t B, int64_t per_sample, int dtype,
+                    void* stream) {
+  VD_REQUIRE(xt && eps_c && x_prev && x0_hist && coef && step && thresh, "null argument");
+  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && n_steps > 0,
+             "bad shape (B=%lld, per_sample=%lld, n_steps=%lld)", (long long)B,
+             (long long)per_sample, (long long)n_steps);
+  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
+  VD_REQUIRE(!eps_u || rescale == 0.f || workspace,
+             "rescale > 0 needs the vd_cfg_stats workspace (null)");
+  DPMStep op{coef, n_steps, step, 0};
+  const CfgGuide gd{w};
+  const int nb = cfg_blocks(per_sample);
+  const float* part = static_cast<const float*>(workspace);
+  hipStream_t st = VD_STREAM(stream);
+  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist});
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (v8)
+      thr_dpm_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
+          (T*)x0_hist, part, nb, rescale, thresh, per_sample);
+    else
+      thr_dpm_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
+          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
+          (T*)x0_hist, part, nb, rescale, thresh, per_sample);
   });
 }
 

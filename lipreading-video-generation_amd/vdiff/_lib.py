@@ -20,6 +20,7 @@ ABI_VERSION = 1
 PREDICTIONS = {"eps": 0, "v": 1}
 LOSS_WEIGHTINGS = {"none": 0, "min-snr": 1}
 WINDOW_KMAX = 8  # VD_WINDOW_KMAX
+X0_IDENTITY, X0_DDIM, X0_DPM = 0, 1, 2  # enum vd_x0_rule
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -52,6 +53,13 @@ class XAttnDesc(C.Structure):
 class EmaDesc(C.Structure):
     """vd_ema_desc: one range of a parameter and of its shadow per rate."""
     _fields_ = [("src", _vp), ("dst", _vp * 4), ("n", _i64)]
+
+
+class X0Source(C.Structure):
+    """vd_x0_source: where vd_x0_abs_quantile's x0 comes from (enum vd_x0_rule)."""
+    _fields_ = [("x", _vp), ("eps", _vp), ("eps_u", _vp), ("t", _vp), ("acp", _vp),
+                ("coef", _vp), ("step", _vp), ("cfg_workspace", _vp), ("n_steps", _i64),
+                ("rule", C.c_int32), ("prediction", C.c_int32), ("w", _f), ("rescale", _f)]
 
 
 class GradDesc(C.Structure):
@@ -101,6 +109,13 @@ _SIGS = {
     "vd_dpm_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _vp]),
     "vd_dpm_step_cfg": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i, _i64,
                              _i64, _i, _vp]),
+    "vd_x0_quantile_workspace_size": (_sz, [_i64, _i64]),
+    "vd_x0_abs_quantile": (_i, [C.POINTER(X0Source), _i64, _f, _f, _i64, _i64, _i, _vp, _vp, _sz,
+                                _vp]),
+    "vd_ddim_step_thr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f,
+                              _i, _vp, _i64, _i64, _i, _vp]),
+    "vd_dpm_step_thr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp,
+                             _i64, _i64, _i, _vp]),
     "vd_window_gather": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
     "vd_window_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i,
                              _vp]),

@@ -20,7 +20,8 @@ import warnings
 import torch
 
 from . import hipgraph, ops
-from .schedulers import DDIMSampler, DPMSolverSampler, WindowPlan, _sqrt_tables
+from .schedulers import (DDIMSampler, DPMSolverSampler, WindowPlan, _sqrt_tables,
+                         _thresh_kw)
 
 
 def _encode(model, audio):
@@ -189,10 +190,10 @@ class DDIMGraph:
         if self.guided:
             _, x0 = ops.ddim_step_cfg(self.xt, *out, self.t[:B], self.tp[:B], self.acp,
                                       self.scale, self.rescale, clip=s.clip_x0, out=self.xt,
-                                      dup=self.dup, prediction=s.prediction)
+                                      dup=self.dup, prediction=s.prediction, **_thresh_kw(s))
             return x0
         xp, x0 = ops.ddim_step(self.xt, out, self.t[:B], self.tp[:B], self.acp, eta=0.0,
-                               clip=s.clip_x0, prediction=s.prediction)
+                               clip=s.clip_x0, prediction=s.prediction, **_thresh_kw(s))
         self.xt.copy_(xp.view_as(self.xt))
         return x0
 
@@ -252,12 +253,13 @@ class DPMGraph(DDIMGraph):
         self.x0 = torch.empty_like(self.xt, memory_format=torch.contiguous_format)
 
     def _update(self, out):
-        clip = self.sampler.clip_x0
+        clip, thr = self.sampler.clip_x0, _thresh_kw(self.sampler)
         if self.guided:
             ops.dpm_step_cfg(self.xt, *out, self.x0, self.coef, self.idx, self.scale,
-                             self.rescale, clip=clip, out=self.xt, dup=self.dup)
+                             self.rescale, clip=clip, out=self.xt, dup=self.dup, **thr)
         else:
-            ops.dpm_step(self.xt, out, self.x0, self.coef, self.idx, clip=clip, out=self.xt)
+            ops.dpm_step(self.xt, out, self.x0, self.coef, self.idx, clip=clip, out=self.xt,
+                         **thr)
         return self.x0
 
 

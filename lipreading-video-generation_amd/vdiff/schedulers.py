@@ -28,6 +28,33 @@ class _Tables:
         return cache[key]
 
 
+def _threshold_option(name, dynamic_threshold, threshold_max, clip_x0):
+    """The samplers' keyword-only dynamic-thresholding option as the step ops take it: None
+    (off) or (p, threshold_max).  Imagen's dynamic thresholding (Saharia et al. 2022, section
+    2.3): every step clamps x0 to [-s, s] and divides by s, s = min(max(q, 1), threshold_max)
+    with q the sample's p-quantile of |x0| (the "higher" order statistic, an element of the
+    data).  It replaces the static clamp, so it excludes clip_x0."""
+    if dynamic_threshold is None:
+        if threshold_max is not None:
+            raise ValueError(f"{name}: threshold_max needs dynamic_threshold")
+        return None
+    p = float(dynamic_threshold)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"{name}: dynamic_threshold {dynamic_threshold} outside (0, 1]")
+    tmax = math.inf if threshold_max is None else float(threshold_max)
+    if not tmax >= 1.0:
+        raise ValueError(f"{name}: threshold_max {threshold_max} < 1")
+    if clip_x0:
+        raise ValueError(f"{name}: dynamic_threshold and clip_x0=True exclude each other")
+    return p, tmax
+
+
+def _thresh_kw(sampler):
+    """{"thresh": (p, threshold_max)} of a sampler built with dynamic_threshold, else {}: with
+    the option off the step ops are called exactly as before."""
+    return {} if sampler.thresh is None else {"thresh": sampler.thresh}
+
+
 def _sqrt_tables(scheduler):
     """(sqrt_acp, sqrt_1m_acp) of a DDPM scheduler as fp32 CPU vectors: the two tables its
     q_sample reads, under either family's attribute names."""
@@ -123,11 +150,15 @@ class DDIMSampler:
     sqrt(1 - a_t) x0, Salimans & Ho 2022): the step kernel then forms x0 = sqrt(a_t) xt -
     sqrt(1 - a_t) v and eps = sqrt(1 - a_t) xt + sqrt(a_t) v itself.  step() and step_guided()
     take the model's output under the name noise_pred / eps_c, eps_u either way.
+    dynamic_threshold=p (keyword-only, with threshold_max; default off): dynamic thresholding
+    of x0 at every step instead of clip_x0 (_threshold_option).
     """
 
-    def __init__(self, scheduler, steps=50, eta=0.0, clip_x0=False, prediction="eps"):
+    def __init__(self, scheduler, steps=50, eta=0.0, clip_x0=False, prediction="eps", *,
+                 dynamic_threshold=None, threshold_max=None):
         ops.prediction_id(prediction)  # ValueError on anything but "eps" / "v"
         self.prediction = prediction
+        self.thresh = _threshold_option("DDIMSampler", dynamic_threshold, threshold_max, clip_x0)
         acp = getattr(scheduler, "alpha_cum_prod", None)
         if acp is None:
             acp = scheduler.alphas_cumprod
@@ -159,7 +190,7 @@ class DDIMSampler:
             z = torch.randn_like(xt)
         return ops.ddim_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), t, tp,
                              self._acp(xt.device), eta=self.eta, z=z, clip=self.clip_x0,
-                             prediction=self.prediction)
+                             prediction=self.prediction, **_thresh_kw(self))
 
     def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, z=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
@@ -170,7 +201,7 @@ class DDIMSampler:
         return ops.ddim_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
                                  eps_u.contiguous().to(xt.dtype), t, tp, self._acp(xt.device),
                                  scale, rescale, eta=self.eta, z=z, clip=self.clip_x0,
-                                 prediction=self.prediction)
+                                 prediction=self.prediction, **_thresh_kw(self))
 
 
 class WindowPlan:
@@ -246,10 +277,14 @@ def _prediction_keyword(init):
     callers and the 2M tests rely on, stay exactly the initialiser's own (functools.wraps: that
     is also the signature introspection reports)."""
     @functools.wraps(init)
-    def with_prediction(self, *args, prediction="eps", **kw):
+    def with_prediction(self, *args, prediction="eps", dynamic_threshold=None,
+                        threshold_max=None, **kw):
         ops.prediction_id(prediction)  # ValueError on anything but "eps" / "v"
         self.prediction = prediction
         init(self, *args, **kw)
+        # keyword-only as prediction is; checked against the clip_x0 the initialiser stored
+        self.thresh = _threshold_option(type(self).__name__, dynamic_threshold, threshold_max,
+                                        self.clip_x0)
     return with_prediction
 
 
@@ -259,8 +294,11 @@ class DPMSolverSampler:
     instead of a second forward, so a step costs what a DDIM step costs.  This is diffusers'
     DPMSolverMultistepScheduler with algorithm_type="dpmsolver++", solver_type="midpoint",
     lower_order_final=True and a zero final sigma, for prediction_type "epsilon" (the default)
-    or "v_prediction" (prediction="v").  Not here: the stochastic (SDE) variants, third-order
-    and singlestep solvers, dynamic thresholding and x0-prediction.
+    or "v_prediction" (prediction="v"), and with diffusers' thresholding=True as
+    dynamic_threshold=p (keyword-only, with threshold_max; _threshold_option): x0 is clamped to
+    [-s, s] and divided by s before it enters x_prev and the history, s from the "higher" order
+    statistic where diffusers interpolates linearly.  Not here: the stochastic (SDE) variants,
+    third-order and singlestep solvers and x0-prediction.
 
     With alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(alpha / sigma), h = lambda_prev -
     lambda_t and k = -alpha_prev expm1(-h), a step is
@@ -376,7 +414,7 @@ class DPMSolverSampler:
         returned.  None is allowed where the row does not read it (C == 0)."""
         hist, coef, idx = self._row(xt, i, x0_last)
         return ops.dpm_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), hist, coef,
-                            idx, clip=self.clip_x0)
+                            idx, clip=self.clip_x0, **_thresh_kw(self))
 
     def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, x0_last=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
@@ -384,4 +422,4 @@ class DPMSolverSampler:
         hist, coef, idx = self._row(xt, i, x0_last)
         return ops.dpm_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
                                 eps_u.contiguous().to(xt.dtype), hist, coef, idx, scale,
-                                rescale, clip=self.clip_x0)
+                                rescale, clip=self.clip_x0, **_thresh_kw(self))

@@ -220,7 +220,24 @@ def parse(argv=None):
                     help="weights of overlapping windows: highest at a window's centre, or equal")
     ap.add_argument("--window-batch", type=int, default=None,
                     help="windows per denoiser forward (default: all of them in one)")
+    ap.add_argument("--dynamic-threshold", type=float, default=None, metavar="P",
+                    help="dynamic thresholding (Saharia et al. 2022): every step clamps x0 to "
+                         "[-s, s] and divides by s, s the sample's P-quantile of |x0|, at least 1 "
+                         "(--sampler ddim|dpm++; for guidance scales well above 1)")
+    ap.add_argument("--threshold-max", type=float, default=None, metavar="M",
+                    help="upper bound of the dynamic threshold s (default: none)")
     args = ap.parse_args(argv)
+    if args.dynamic_threshold is not None:
+        if args.sampler not in ("ddim", "dpm++"):
+            ap.error(f"--dynamic-threshold needs --sampler ddim or dpm++ (got {args.sampler}: "
+                     "ancestral DDPM has no x0 clamp to replace)")
+        if not 0.0 < args.dynamic_threshold <= 1.0:
+            ap.error("--dynamic-threshold must be in (0, 1]")
+    if args.threshold_max is not None:
+        if args.dynamic_threshold is None:
+            ap.error("--threshold-max needs --dynamic-threshold")
+        if not args.threshold_max >= 1.0:
+            ap.error("--threshold-max must be at least 1")
     if args.steps is None and args.sampler == "dpm++":
         args.steps = 20
     if args.clip_frames is not None:
@@ -284,11 +301,15 @@ def main(argv=None):
         shape = (1, 3, frames, args.image_size, args.image_size) if args.dims == 3 else \
             (1, 3, args.image_size, args.image_size)
         if args.sampler == "ddim":
-            sampler = DDIMSampler(scheduler, steps=args.steps or 50, prediction=args.prediction)
+            sampler = DDIMSampler(scheduler, steps=args.steps or 50, prediction=args.prediction,
+                                  dynamic_threshold=args.dynamic_threshold,
+                                  threshold_max=args.threshold_max)
             sample = sample_ddim
         else:
             sampler = DPMSolverSampler(scheduler, steps=args.steps or 20, spacing=args.spacing,
-                                       prediction=args.prediction)
+                                       prediction=args.prediction,
+                                       dynamic_threshold=args.dynamic_threshold,
+                                       threshold_max=args.threshold_max)
             sample = sample_dpm
 
         def cb(i, xt, x0):
