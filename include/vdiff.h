@@ -164,8 +164,8 @@ int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev,
                  const float* acp, float eta, int clip, int64_t B,
                  int64_t per_sample, int dtype, void* stream);
 /* The same step for a model output of either parameterisation (enum vd_prediction, above).
- * VD_PRED_EPS: vd_ddim_step's own kernel, the same bits.  VD_PRED_V: `eps` holds the model's v
- * and, with sa = sqrt(a_t), s1m = sqrt(1 - a_t),
+ * VD_PRED_EPS: vd_ddim_step (which is this call).  VD_PRED_V: `eps` holds the model's v and,
+ * with sa = sqrt(a_t), s1m = sqrt(1 - a_t),
  *   x0 = sa xt - s1m v,  eps = s1m xt + sa v;
  * the clamp, the direction and the noise terms are as above. */
 int vd_ddim_step_pred(const void* xt, const void* eps, const void* z, void* x_prev,
@@ -206,8 +206,11 @@ int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w,
                    void* stream);
 /* vd_ddim_step_cfg for either parameterisation: the guide and the std-rescale act on the model
  * output -- with VD_PRED_V on the two v outputs, as Lin et al. define the rescale -- and the
- * guided output enters the step as in vd_ddim_step_pred.  VD_PRED_EPS: vd_ddim_step_cfg's own
- * kernel, the same bits. */
+ * guided output enters the step as in vd_ddim_step_pred.  VD_PRED_EPS: vd_ddim_step_cfg (which
+ * is this call).
+ * Every DDIM and DPM-Solver++ step entry point, plain, guided or thresholded, launches one
+ * instantiation of the same step kernel (csrc/elementwise.hip, step_kernel): one block column
+ * per sample, the sample's schedule scalars, f_b and threshold taken once per block. */
 int vd_ddim_step_cfg_pred(const void* xt, const void* eps_c, const void* eps_u, const void* z,
                           void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
                           const int64_t* t_prev, const float* acp, float w, float rescale,

@@ -1,5 +1,7 @@
 // elementwise.hip -- HBM-bound wave-level kernels of the diffusion hot path:
-// timestep embedding, DDPM/DDIM scheduler math and nearest upsampling.
+// timestep embedding, DDPM scheduler math, classifier-free guidance, the DDIM / DPM-Solver++
+// sampler step with its dynamic threshold, nearest upsampling, the MSE loss, conv glue and the
+// weight EMA.
 //
 // Every tensor kernel moves 8 elements per lane (16 B for bf16, 2x16 B for
 // fp32) when the per-sample length allows it, and gathers the per-sample
@@ -7,6 +9,7 @@
 #include "vd_common.h"
 #include <math.h>
 #include <initializer_list>
+#include <type_traits>
 
 namespace {
 
@@ -109,51 +112,6 @@ struct PSampleCos {
   }
 };
 
-struct DDIMStep {
-  const float* acp;
-  const int64_t* tprev;
-  float eta;
-  int clip;
-  int has_z;
-  // b index is passed through tb via the high bits? no: operator gets tb and b.
-  // PRED_V: `eps` holds the model's v (Salimans & Ho 2022): x0 = sqrt(a_t) xt - sqrt(1 - a_t) v,
-  // eps = sqrt(1 - a_t) xt + sqrt(a_t) v; clip, direction and noise terms are the same.  The
-  // eps instantiation is the code it was before the template parameter: the same bits.
-  // THR (dynamic thresholding, vd_ddim_step_thr): x0 = clamp(x0, -s, s) / s with the sample's
-  // s = thr[b] >= 1 of vd_x0_abs_quantile; the direction term keeps the model's own eps, as
-  // clip does.  THR = false is the code it was before this parameter too.
-  template <bool PRED_V, bool THR = false>
-  __device__ void run(int64_t tb, int64_t tp, const float* xt, const float* eps, const float* z,
-                      float* xprev, float* x0o, int n, float s = 1.f) const {
-    const float at = acp[tb];
-    const float ap = tp >= 0 ? acp[tp] : 1.f;
-    const float sq_at = sqrtf(at), sq_1mat = sqrtf(1.f - at);
-    const float sigma = eta * sqrtf((1.f - ap) / (1.f - at) * (1.f - at / ap));
-    const float dir = sqrtf(fmaxf(1.f - ap - sigma * sigma, 0.f));
-    const float sq_ap = sqrtf(ap);
-    for (int i = 0; i < n; ++i) {
-      if constexpr (PRED_V) {
-        float x0 = sq_at * xt[i] - sq_1mat * eps[i];
-        const float e = sq_1mat * xt[i] + sq_at * eps[i];
-        if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-        if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
-        x0o[i] = x0;
-        float v = sq_ap * x0 + dir * e;
-        if (has_z) v += sigma * z[i];
-        xprev[i] = v;
-      } else {
-        float x0 = (xt[i] - sq_1mat * eps[i]) / sq_at;
-        if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-        if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
-        x0o[i] = x0;
-        float v = sq_ap * x0 + dir * eps[i];
-        if (has_z) v += sigma * z[i];
-        xprev[i] = v;
-      }
-    }
-  }
-};
-
 template <typename T>
 __device__ __forceinline__ void ld_vec(const T* p, float (&v)[8], int n) {
   if (n == 8) {
@@ -188,25 +146,6 @@ __global__ void sched_kernel(Op op, const T* __restrict__ a, const T* __restrict
     op(t[bi], xa, xb, xc, y0, y1, VEC);
     st_vec(o0 + e, y0, VEC);
     if (o1) st_vec(o1 + e, y1, VEC);
-  }
-}
-
-template <typename T, int VEC, bool PRED_V>
-__global__ void ddim_kernel(DDIMStep op, const T* __restrict__ xt, const T* __restrict__ eps,
-                            const T* __restrict__ z, T* __restrict__ xprev, T* __restrict__ x0,
-                            const int64_t* __restrict__ t, int64_t B, int64_t per_sample) {
-  const int64_t nvec = B * per_sample / VEC;
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e = v * VEC;
-    const int64_t bi = e / per_sample;
-    float xa[8], xb[8], xc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, y0[8], y1[8];
-    ld_vec(xt + e, xa, VEC);
-    ld_vec(eps + e, xb, VEC);
-    if (z) ld_vec(z + e, xc, VEC);
-    op.run<PRED_V>(t[bi], op.tprev[bi], xa, xb, xc, y0, y1, VEC);
-    st_vec(xprev + e, y0, VEC);
-    if (x0) st_vec(x0 + e, y1, VEC);
   }
 }
 
@@ -495,38 +434,25 @@ __device__ __forceinline__ float cfg_factor(const float* __restrict__ part, int6
   return phi * sqrtf(qc / qg) + (1.f - phi);
 }
 
-// Guide + rescale + DDIM step in one pass: reads xt, c, u (and z), writes x_prev (twice when
-// xdup is given: the graph sampler's doubled-batch input) and x0.  blockIdx.y = sample, so a
-// block takes f_b once; x_prev may alias xt (a lane reads its elements before it writes them).
-template <typename T, int VEC, bool PRED_V>
-__global__ void __launch_bounds__(kBlock) cfg_ddim_kernel(
-    DDIMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
-    const T* __restrict__ z, T* xprev, T* xdup, T* __restrict__ x0,
-    const int64_t* __restrict__ t, const float* __restrict__ part, int nb, float phi,
-    int64_t per_sample) {
-  const int64_t b = blockIdx.y;
-  const bool scale = phi > 0.f;
-  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
-  const int64_t tb = t[b], tp = op.tprev[b];
-  const int64_t base = b * per_sample;
-  const int64_t nvec = per_sample / VEC;
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e = base + v * VEC;
-    float xa[8], xc[8], xu[8], xz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
-    ld_vec(xt + e, xa, VEC);
-    ld_vec(c + e, xc, VEC);
-    ld_vec(u + e, xu, VEC);
-    if (z) ld_vec(z + e, xz, VEC);
-    gd.run(xc, xu, f, scale, g, VEC);
-    op.run<PRED_V>(tb, tp, xa, g, xz, y0, y1, VEC);
-    st_vec(xprev + e, y0, VEC);
-    if (xdup) st_vec(xdup + e, y0, VEC);
-    if (x0) st_vec(x0 + e, y1, VEC);
+// The model output of one vector, shared by every consumer (the combine, the sampler step, the
+// x0 histogram): c as it is, or, guided, CfgGuide::run(c, u, f, scale).  `guided` is a constant
+// where the caller knows it: a test of the pointer itself would hold u's load back behind c's.
+template <typename T, int VEC>
+__device__ __forceinline__ void model_out(const T* c, const T* u, bool guided, const CfgGuide& gd,
+                                          float f, bool scale, float (&m)[8]) {
+  float xc[8];
+  ld_vec(c, xc, VEC);
+  if (guided) {
+    float xu[8];
+    ld_vec(u, xu, VEC);
+    gd.run(xc, xu, f, scale, m, VEC);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) m[k] = xc[k];
   }
 }
 
-// The same guided noise written out (the DDPM p_sample_* kernels take it as their eps).
+// The guided noise written out (the DDPM p_sample_* kernels take it as their eps).
 template <typename T, int VEC>
 __global__ void __launch_bounds__(kBlock) cfg_combine_kernel(
     CfgGuide gd, const T* __restrict__ c, const T* __restrict__ u, T* __restrict__ out,
@@ -539,116 +465,156 @@ __global__ void __launch_bounds__(kBlock) cfg_combine_kernel(
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
        v += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e = base + v * VEC;
-    float xc[8], xu[8], g[8];
-    ld_vec(c + e, xc, VEC);
-    ld_vec(u + e, xu, VEC);
-    gd.run(xc, xu, f, scale, g, VEC);
+    float g[8];
+    model_out<T, VEC>(c + e, u + e, true, gd, f, scale, g);
     st_vec(out + e, g, VEC);
   }
 }
 
-// ------------------------------------------------------------ DPM-Solver++(2M) step
-// x0 = (xt - sigma_t eps) / alpha_t, x_prev = A xt + B x0 + C x0_last, with the row [alpha_t,
-// sigma_t, A, B, C, 0, 0, 0] of the host's fp32 table picked by a device scalar: the launch
-// arguments never change, so a captured graph replays for every step.  The row is uniform
-// across the launch.  C == 0 (the first-order rows and the last one): the history is not read
-// -- at step 0 it is uninitialised, and 0 * NaN is NaN.
-struct DPMStep {
-  const float* coef;
-  int64_t n_steps;
-  const int64_t* step;
-  int clip;
-  struct Row {
-    float alpha, sigma, A, B, C;
-  };
-  __device__ __forceinline__ Row row() const {
-    int64_t s = *step;
-    s = s < 0 ? 0 : (s > n_steps - 1 ? n_steps - 1 : s);
-    const float* r = coef + s * 8;
-    return Row{r[0], r[1], r[2], r[3], r[4]};
+// One block column per sample: sample b is row b % 65535 of layer b / 65535 (a grid has at most
+// 65535 rows; the entry points that check B <= 65535 launch one layer).
+constexpr int64_t kGridRows = 65535;
+inline dim3 cfg_grid(int64_t per_sample, int vec, int64_t B) {
+  return dim3((unsigned)grid_for(per_sample / vec), (unsigned)(B < kGridRows ? B : kGridRows),
+              (unsigned)vd_cdiv(B, kGridRows));
+}
+
+// ------------------------------------------------------------ sampler step (DDIM, DPM-Solver++)
+// A rule is two per-element pieces, x0 from (xt, model output) and x_prev from (xt, x0,
+// direction term, third input), and carries its scalars: sample_x0(b) takes those of the x0
+// piece (all the x0 histogram needs), sample(b) those of both.
+//
+// DDIM (Song et al. 2021): x0 = (xt - sqrt(1 - a_t) eps) / sqrt(a_t), x_prev = sqrt(a_p) x0 +
+// dir eps (+ sigma z), a_t = acp[t[b]], a_p = acp[t_prev[b]] (1 for t_prev = -1).  PRED_V: the
+// model output is v (Salimans & Ho 2022): x0 = sqrt(a_t) xt - sqrt(1 - a_t) v, and the direction
+// term is eps = sqrt(1 - a_t) xt + sqrt(a_t) v.  A clamped or thresholded x0 leaves the direction
+// term the model's own.  The third input is z, read when it is given.
+struct DDIMScalars {
+  const float* acp;
+  const int64_t *t, *tprev;
+  float eta;
+  int has_z;
+  float at, sq_at, sq_1mat, sigma, dir, sq_ap;
+  __device__ __forceinline__ void sample_x0(int64_t b) {
+    at = acp[t[b]];
+    sq_at = sqrtf(at), sq_1mat = sqrtf(1.f - at);
   }
-  // x_prev is formed from the fp32 x0, not from the value a bf16 history rounds it to.
-  // THR: the thresholded x0 of DDIMStep::run (vd_dpm_step_thr); it is what x_prev and the
-  // history get.
-  template <bool THR = false>
-  __device__ __forceinline__ void run(const Row& r, bool hist, const float* xt, const float* eps,
-                                      const float* last, float* xprev, float* x0o, int n,
-                                      float s = 1.f) const {
-    for (int i = 0; i < n; ++i) {
-      float x0 = (xt[i] - r.sigma * eps[i]) / r.alpha;
-      if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
-      if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
-      x0o[i] = x0;
-      float v = r.A * xt[i] + r.B * x0;
-      if (hist) v += r.C * last[i];
-      xprev[i] = v;
-    }
+  __device__ __forceinline__ void sample(int64_t b) {
+    sample_x0(b);
+    const int64_t tp = tprev[b];
+    const float ap = tp >= 0 ? acp[tp] : 1.f;
+    sigma = eta * sqrtf((1.f - ap) / (1.f - at) * (1.f - at / ap));
+    dir = sqrtf(fmaxf(1.f - ap - sigma * sigma, 0.f));
+    sq_ap = sqrtf(ap);
+  }
+  __device__ __forceinline__ bool third() const { return has_z; }
+  __device__ __forceinline__ float x_prev(float, float x0, float e, float z) const {
+    float v = sq_ap * x0 + dir * e;
+    if (has_z) v += sigma * z;
+    return v;
+  }
+};
+template <bool PRED_V>
+struct DDIMRule : DDIMScalars {
+  __device__ __forceinline__ float x0(float xt, float m) const {
+    if constexpr (PRED_V)
+      return sq_at * xt - sq_1mat * m;
+    else
+      return (xt - sq_1mat * m) / sq_at;
+  }
+  __device__ __forceinline__ float direction(float xt, float m) const {
+    if constexpr (PRED_V)
+      return sq_1mat * xt + sq_at * m;
+    else
+      return m;
   }
 };
 
-// Three reads (xt, eps, the history when C != 0), two writes (x_prev, the history in place).
-// xprev may alias xt and `hist` is read and written: a lane reads its elements before it
-// writes them, and no other lane touches them.
-template <typename T, int VEC>
-__global__ void __launch_bounds__(kBlock) dpm_kernel(DPMStep op, const T* xt,
-                                                     const T* __restrict__ eps, T* xprev,
-                                                     T* hist, int64_t n) {
-  const DPMStep::Row r = op.row();
-  const bool use_hist = r.C != 0.f;
-  const int64_t nvec = n / VEC;
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e = v * VEC;
-    float xa[8], xb[8], xh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, y0[8], y1[8];
-    ld_vec(xt + e, xa, VEC);
-    ld_vec(eps + e, xb, VEC);
-    if (use_hist) ld_vec(hist + e, xh, VEC);
-    op.run(r, use_hist, xa, xb, xh, y0, y1, VEC);
-    st_vec(xprev + e, y0, VEC);
-    st_vec(hist + e, y1, VEC);
+// DPM-Solver++(2M): x0 = (xt - sigma_t eps) / alpha_t, x_prev = A xt + B x0 + C x0_last, with
+// the row [alpha_t, sigma_t, A, B, C, 0, 0, 0] of the host's fp32 table picked by a device
+// scalar: the launch arguments never change, so a captured graph replays for every step.  The
+// row is uniform across the launch.  The third input is the history, x0_last; C == 0 (the
+// first-order rows and the last one): it is not read -- at step 0 it is uninitialised, and
+// 0 * NaN is NaN.  x_prev is formed from the fp32 x0, not from the value a bf16 history rounds
+// it to.
+struct DPMRule {
+  const float* coef;
+  int64_t n_steps;
+  const int64_t* step;
+  float alpha, sigma, A, B, C;
+  __device__ __forceinline__ void sample_x0(int64_t) {
+    int64_t s = *step;
+    s = s < 0 ? 0 : (s > n_steps - 1 ? n_steps - 1 : s);
+    const float* r = coef + s * 8;
+    alpha = r[0], sigma = r[1], A = r[2], B = r[3], C = r[4];
   }
-}
+  __device__ __forceinline__ void sample(int64_t b) { sample_x0(b); }
+  __device__ __forceinline__ bool third() const { return C != 0.f; }
+  __device__ __forceinline__ float x0(float xt, float m) const { return (xt - sigma * m) / alpha; }
+  __device__ __forceinline__ float direction(float, float m) const { return m; }
+  __device__ __forceinline__ float x_prev(float xt, float x0, float, float last) const {
+    float v = A * xt + B * x0;
+    if (C != 0.f) v += C * last;
+    return v;
+  }
+};
 
-// Guide + rescale + the step above in one pass, laid out as cfg_ddim_kernel: blockIdx.y =
-// sample, one f_b per block, x_prev written twice when xdup is given.
-template <typename T, int VEC>
-__global__ void __launch_bounds__(kBlock) cfg_dpm_kernel(
-    DPMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
-    T* xprev, T* xdup, T* hist, const float* __restrict__ part, int nb, float phi,
-    int64_t per_sample) {
-  const int64_t b = blockIdx.y;
-  const bool scale = phi > 0.f;
+// The one step kernel: model output (guided and std-rescaled when GUIDED) -> x0 -> static clamp
+// (clip) or, THR, the dynamic threshold x0 = clamp(x0, -s, s) / s with the sample's s = thr[b]
+// >= 1 of vd_x0_abs_quantile -> x_prev.  Reads xt, c (u) and the rule's third input (z | the
+// history); writes x_prev, xdup (the same values: the graph sampler's doubled-batch input) and x0,
+// the latter two when given.  A block works on one sample (cfg_grid), so it takes the sample's
+// scalars, f_b and s_b once, from scalar loads ahead of every store.
+// Aliasing: x_prev may be xt, and the DPM history arrives as both `third` and `x0o`, read and
+// written in place: a lane reads its elements before it writes them and no other lane touches
+// them, so xt, third, xprev, xdup and x0o carry no __restrict__.
+template <typename T, int VEC, typename Rule, bool THR, bool GUIDED>
+__global__ void __launch_bounds__(kBlock) step_kernel(
+    Rule rule, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
+    const T* third, T* xprev, T* xdup, T* x0o, const float* __restrict__ part, int nb, float phi,
+    const float* __restrict__ thr, int clip, int64_t B, int64_t per_sample) {
+  // The sample: the row, strided over the grid's rows by the layer (cfg_grid).  A row past B (the
+  // last layer's) takes the last sample's scalars and an empty range: an early return would hold
+  // every other argument's load back behind B's.
+  const int64_t row = blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
+  const int64_t b = row < B ? row : B - 1;
+  // the rule's scalars first: their dependent loads run beside the sum of f_b's partials
+  rule.sample(b);
+  const bool has3 = rule.third();
+  const float s = THR ? thr[b] : 1.f;
+  const bool scale = GUIDED && phi > 0.f;
   const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
-  const DPMStep::Row r = op.row();
-  const bool use_hist = r.C != 0.f;
   const int64_t base = b * per_sample;
-  const int64_t nvec = per_sample / VEC;
+  const int64_t nvec = row < B ? per_sample / VEC : 0;
   for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
        v += (int64_t)gridDim.x * blockDim.x) {
     const int64_t e = base + v * VEC;
-    float xa[8], xc[8], xu[8], xh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
+    float xa[8], m[8], x3[8] = {0, 0, 0, 0, 0, 0, 0, 0}, y0[8], y1[8];
     ld_vec(xt + e, xa, VEC);
-    ld_vec(c + e, xc, VEC);
-    ld_vec(u + e, xu, VEC);
-    if (use_hist) ld_vec(hist + e, xh, VEC);
-    gd.run(xc, xu, f, scale, g, VEC);
-    op.run(r, use_hist, xa, g, xh, y0, y1, VEC);
+    model_out<T, VEC>(c + e, GUIDED ? u + e : nullptr, GUIDED, gd, f, scale, m);
+    if (has3) ld_vec(third + e, x3, VEC);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      float x0 = rule.x0(xa[i], m[i]);
+      if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+      if constexpr (THR) x0 = fminf(fmaxf(x0, -s), s) / s;
+      y1[i] = x0;
+      y0[i] = rule.x_prev(xa[i], x0, rule.direction(xa[i], m[i]), x3[i]);
+    }
     st_vec(xprev + e, y0, VEC);
     if (xdup) st_vec(xdup + e, y0, VEC);
-    st_vec(hist + e, y1, VEC);
+    if (x0o) st_vec(x0o + e, y1, VEC);
   }
-}
-
-inline dim3 cfg_grid(int64_t per_sample, int vec, int64_t B) {
-  return dim3((unsigned)grid_for(per_sample / vec), (unsigned)B);
 }
 
 // ------------------------------------------------------------ dynamic thresholding
 // s_b = min(max(q_b, floor), cap), q_b the rank-th smallest |x0| of sample b (0-based; an element
 // of the data): Imagen's dynamic threshold (Saharia et al. 2022, section 2.3) with the "higher"
 // order statistic.  x0 is never written to memory: every pass forms it again from the step's
-// inputs with the step kernels' own code -- DDIMStep::run / DPMStep::run without the clamp, after
-// CfgGuide::run and cfg_factor -- so it has the bits the thresholded step sees.
+// inputs with the step kernel's own source -- the rule's x0 piece on model_out's vector, with
+// cfg_factor's f_b.  The step kernel is another instantiation: where an x0 has two products (v)
+// the compiler picks per instantiation which one it fuses, so the step's x0 can differ from this
+// one in the last bit (inside the bound the tests hold s to, tests/_thr_cases.py).
 //
 // Method: a most-significant-digit radix select over the bit pattern of |x0| (non-negative
 // floats order as their uint32 patterns; a NaN sorts above +inf), four 8-bit digits, EIGHT
@@ -675,9 +641,8 @@ static_assert(kThrBins == kBlock, "x0_hist_kernel: thread d stores bin d");
 struct X0Source {
   int rule;
   bool pred_v;
-  DDIMStep ddim;
-  const int64_t* t;
-  DPMStep dpm;
+  DDIMScalars ddim;
+  DPMRule dpm;
   CfgGuide gd;
   const float* part;
   int nb_cfg;
@@ -702,10 +667,8 @@ __global__ void __launch_bounds__(kBlock) x0_hist_kernel(
   const int hi = first ? 0 : shift + 8;
   for (int i = threadIdx.x; i < kThrBins * kThrCopies; i += kBlock) hist[i] = 0u;
   __syncthreads();
-  int64_t tb = 0;
-  DPMStep::Row r{};
-  if (src.rule == VD_X0_DDIM) tb = src.t[b];
-  if (src.rule == VD_X0_DPM) r = src.dpm.row();
+  if (src.rule == VD_X0_DDIM) src.ddim.sample_x0(b);
+  if (src.rule == VD_X0_DPM) src.dpm.sample_x0(b);
   const int64_t lo = (int64_t)blockIdx.x * chunk;
   const int64_t end = lo + chunk < P ? lo + chunk : P;
   const int64_t base = b * P;
@@ -718,22 +681,18 @@ __global__ void __launch_bounds__(kBlock) x0_hist_kernel(
 #pragma unroll
       for (int k = 0; k < VEC; ++k) x0[k] = xa[k];
     } else {
-      float xc[8], g[8], xz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, y0[8];
-      ld_vec(c + e, xc, VEC);
-      if (guided) {
-        float xu[8];
-        ld_vec(u + e, xu, VEC);
-        src.gd.run(xc, xu, f, scale, g, VEC);
-      } else {
+      float m[8];
+      model_out<T, VEC>(c + e, guided ? u + e : nullptr, guided, src.gd, f, scale, m);
+      auto form = [&](const auto& rule) {
 #pragma unroll
-        for (int k = 0; k < VEC; ++k) g[k] = xc[k];
-      }
+        for (int k = 0; k < VEC; ++k) x0[k] = rule.x0(xa[k], m[k]);
+      };
       if (src.rule == VD_X0_DPM)
-        src.dpm.run(r, false, xa, g, xz, y0, x0, VEC);
+        form(src.dpm);
       else if (src.pred_v)
-        src.ddim.run<true>(tb, -1, xa, g, xz, y0, x0, VEC);
+        form(DDIMRule<true>{src.ddim});
       else
-        src.ddim.run<false>(tb, -1, xa, g, xz, y0, x0, VEC);
+        form(DDIMRule<false>{src.ddim});
     }
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
@@ -802,79 +761,153 @@ __global__ void __launch_bounds__(kThrBins* kThrScanParts)
   }
 }
 
-// Guide (u != nullptr) + rescale + the thresholded DDIM step: cfg_ddim_kernel's layout
-// (blockIdx.y = sample, x_prev may alias xt, xdup gets x_prev's values) with s = thr[b].
-template <typename T, int VEC, bool PRED_V>
-__global__ void __launch_bounds__(kBlock) thr_ddim_kernel(
-    DDIMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
-    const T* __restrict__ z, T* xprev, T* xdup, T* __restrict__ x0,
-    const int64_t* __restrict__ t, const float* __restrict__ part, int nb, float phi,
-    const float* __restrict__ thr, int64_t per_sample) {
-  const int64_t b = blockIdx.y;
-  const bool guided = u != nullptr;
-  const bool scale = guided && phi > 0.f;
-  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
-  const float s = thr[b];
-  const int64_t tb = t[b], tp = op.tprev[b];
-  const int64_t base = b * per_sample;
-  const int64_t nvec = per_sample / VEC;
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e = base + v * VEC;
-    float xa[8], xc[8], xz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
-    ld_vec(xt + e, xa, VEC);
-    ld_vec(c + e, xc, VEC);
-    if (guided) {
-      float xu[8];
-      ld_vec(u + e, xu, VEC);
-      gd.run(xc, xu, f, scale, g, VEC);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) g[k] = xc[k];
-    }
-    if (z) ld_vec(z + e, xz, VEC);
-    op.run<PRED_V, true>(tb, tp, xa, g, xz, y0, y1, VEC, s);
-    st_vec(xprev + e, y0, VEC);
-    if (xdup) st_vec(xdup + e, y0, VEC);
-    if (x0) st_vec(x0 + e, y1, VEC);
-  }
+// ------------------------------------------------------------ sampler step: host side
+// What the eight step entry points hand to check_step and launch_step.  c / u: the model output
+// with / without the audio (u NULL: unguided); third: z (DDIM) or the history (DPM), x0 the
+// optional x0 output (DDIM) or the history again (DPM); thresh non-NULL: the thresholded step.
+struct StepArgs {
+  int rule = VD_X0_DDIM;  // VD_X0_DDIM | VD_X0_DPM
+  int prediction = VD_PRED_EPS;
+  const void *xt = nullptr, *c = nullptr, *u = nullptr, *third = nullptr;
+  void *xprev = nullptr, *xdup = nullptr, *x0 = nullptr;
+  const int64_t *t = nullptr, *tprev = nullptr;  // DDIM
+  const float* acp = nullptr;
+  float eta = 0.f;
+  const float* coef = nullptr;  // DPM
+  int64_t n_steps = 0;
+  const int64_t* step = nullptr;
+  float w = 1.f, rescale = 0.f;
+  const void* workspace = nullptr;
+  const float* thresh = nullptr;
+  int clip = 0;
+  int64_t B = 0, per_sample = 0;
+};
+
+// The one place a rule is built: launch_step and vd_x0_abs_quantile (t_prev NULL: its x0 piece
+// alone) both take theirs from here.
+inline DDIMScalars make_ddim(const float* acp, const int64_t* t, const int64_t* tprev, float eta,
+                             bool has_z) {
+  DDIMScalars r = {};
+  r.acp = acp, r.t = t, r.tprev = tprev, r.eta = eta, r.has_z = has_z;
+  return r;
+}
+inline DPMRule make_dpm(const float* coef, int64_t n_steps, const int64_t* step) {
+  DPMRule r = {};
+  r.coef = coef, r.n_steps = n_steps, r.step = step;
+  return r;
 }
 
-// The same for the DPM-Solver++(2M) step: cfg_dpm_kernel's layout and aliasing rules.
-template <typename T, int VEC>
-__global__ void __launch_bounds__(kBlock) thr_dpm_kernel(
-    DPMStep op, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
-    T* xprev, T* xdup, T* hist, const float* __restrict__ part, int nb, float phi,
-    const float* __restrict__ thr, int64_t per_sample) {
-  const int64_t b = blockIdx.y;
-  const bool guided = u != nullptr;
-  const bool scale = guided && phi > 0.f;
-  const float f = scale ? cfg_factor(part, b, nb, phi) : 1.f;
-  const float s = thr[b];
-  const DPMStep::Row r = op.row();
-  const bool use_hist = r.C != 0.f;
-  const int64_t base = b * per_sample;
-  const int64_t nvec = per_sample / VEC;
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
-       v += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t e = base + v * VEC;
-    float xa[8], xc[8], xh[8] = {0, 0, 0, 0, 0, 0, 0, 0}, g[8], y0[8], y1[8];
-    ld_vec(xt + e, xa, VEC);
-    ld_vec(c + e, xc, VEC);
-    if (guided) {
-      float xu[8];
-      ld_vec(u + e, xu, VEC);
-      gd.run(xc, xu, f, scale, g, VEC);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) g[k] = xc[k];
-    }
-    if (use_hist) ld_vec(hist + e, xh, VEC);
-    op.run<true>(r, use_hist, xa, g, xh, y0, y1, VEC, s);
-    st_vec(xprev + e, y0, VEC);
-    if (xdup) st_vec(xdup + e, y0, VEC);
-    st_vec(hist + e, y1, VEC);
+enum StepKind { STEP_PLAIN, STEP_CFG, STEP_THR };
+
+// The conditions the entry points share.  STEP_PLAIN takes any B (cfg_grid adds a layer of rows
+// for every 65535 samples); STEP_CFG needs u; STEP_THR needs thresh, and the workspace only
+// when guided.
+int check_step(const StepArgs& a, StepKind kind) {
+  const bool dpm = a.rule == VD_X0_DPM;
+  VD_REQUIRE(a.xt && a.c && a.xprev && (kind != STEP_CFG || a.u) && (kind != STEP_THR || a.thresh)
+                 && (dpm ? a.x0 && a.coef && a.step : a.t && a.tprev && a.acp),
+             "null argument");
+  const bool shape_ok = a.B > 0 && (kind == STEP_PLAIN || a.B <= 65535) && a.per_sample > 0;
+  const char* bad =
+      kind != STEP_PLAIN ? "bad shape" : (dpm ? "empty tensor or table" : "empty tensor");
+  if (dpm)
+    VD_REQUIRE(shape_ok && a.n_steps > 0, "%s (B=%lld, per_sample=%lld, n_steps=%lld)", bad,
+               (long long)a.B, (long long)a.per_sample, (long long)a.n_steps);
+  else
+    VD_REQUIRE(shape_ok, "%s (B=%lld, per_sample=%lld)", bad, (long long)a.B,
+               (long long)a.per_sample);
+  if (kind != STEP_PLAIN) {
+    VD_REQUIRE(a.rescale >= 0.f && a.rescale <= 1.f, "rescale %g outside [0, 1]",
+               (double)a.rescale);
+    VD_REQUIRE(!a.u || a.rescale == 0.f || a.workspace,
+               "rescale > 0 needs the vd_cfg_stats workspace (null)");
   }
+  if (!dpm) {
+    VD_REQUIRE(a.eta == 0.f || a.third, "eta > 0 needs z");
+    VD_REQUIRE(a.prediction == VD_PRED_EPS || a.prediction == VD_PRED_V,
+               "unknown prediction type %d", a.prediction);
+  }
+  return VD_OK;
+}
+
+template <typename F>
+void dispatch_bool(bool v, F&& f) {
+  if (v)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+template <typename T, typename Rule>
+void launch_rule(const Rule& rule, const StepArgs& a, hipStream_t st) {
+  const bool v8 = cfg_vec8(a.per_sample, {a.xt, a.c, a.u, a.third, a.xprev, a.xdup, a.x0});
+  const dim3 grid = cfg_grid(a.per_sample, v8 ? 8 : 1, a.B);
+  dispatch_bool(v8, [&](auto V8) {
+    dispatch_bool(a.thresh != nullptr, [&](auto THR) {
+      dispatch_bool(a.u != nullptr, [&](auto GUIDED) {
+        step_kernel<T, decltype(V8)::value ? 8 : 1, Rule, decltype(THR)::value,
+                    decltype(GUIDED)::value><<<grid, kBlock, 0, st>>>(
+            rule, CfgGuide{a.w}, (const T*)a.xt, (const T*)a.c, (const T*)a.u, (const T*)a.third,
+            (T*)a.xprev, (T*)a.xdup, (T*)a.x0, static_cast<const float*>(a.workspace),
+            cfg_blocks(a.per_sample), a.rescale, a.thresh, a.clip, a.B, a.per_sample);
+      });
+    });
+  });
+}
+
+// Vector width (cfg_vec8 over all non-null pointers), grid, and the dispatch over dtype, rule,
+// threshold, guidance and VEC: one launch line.
+int launch_step(const StepArgs& a, int dtype, void* stream) {
+  hipStream_t st = VD_STREAM(stream);
+  return VD_DISPATCH_DTYPE(dtype, T, {
+    if (a.rule == VD_X0_DPM) {
+      launch_rule<T>(make_dpm(a.coef, a.n_steps, a.step), a, st);
+    } else {
+      const DDIMScalars r = make_ddim(a.acp, a.t, a.tprev, a.eta, a.third != nullptr);
+      if (a.prediction == VD_PRED_V)
+        launch_rule<T>(DDIMRule<true>{r}, a, st);
+      else
+        launch_rule<T>(DDIMRule<false>{r}, a, st);
+    }
+  });
+}
+
+// A DDIM step's arguments as every DDIM entry point fills them.
+StepArgs ddim_args(const void* xt, const void* c, const void* u, const void* z, void* x_prev,
+                   void* x_prev_dup, void* x0, const int64_t* t, const int64_t* t_prev,
+                   const float* acp, float eta, int clip, int prediction, int64_t B,
+                   int64_t per_sample) {
+  StepArgs a;
+  a.prediction = prediction;
+  a.xt = xt, a.c = c, a.u = u, a.third = z;
+  a.xprev = x_prev, a.xdup = x_prev_dup, a.x0 = x0;
+  a.t = t, a.tprev = t_prev, a.acp = acp, a.eta = eta, a.clip = clip;
+  a.B = B, a.per_sample = per_sample;
+  return a;
+}
+
+// The same for DPM-Solver++: the history is the third input and the x0 output.
+StepArgs dpm_args(const void* xt, const void* c, const void* u, void* x_prev, void* x_prev_dup,
+                  void* x0_hist, const float* coef, int64_t n_steps, const int64_t* step, int clip,
+                  int64_t B, int64_t per_sample) {
+  StepArgs a;
+  a.rule = VD_X0_DPM;
+  a.xt = xt, a.c = c, a.u = u, a.third = x0_hist;
+  a.xprev = x_prev, a.xdup = x_prev_dup, a.x0 = x0_hist;
+  a.coef = coef, a.n_steps = n_steps, a.step = step, a.clip = clip;
+  a.B = B, a.per_sample = per_sample;
+  return a;
+}
+
+// w, rescale and workspace of a guided or thresholded step
+StepArgs guided(StepArgs a, float w, float rescale, const void* workspace, const float* thresh) {
+  a.w = w, a.rescale = rescale, a.workspace = workspace, a.thresh = thresh;
+  return a;
+}
+
+int run_step(const StepArgs& a, StepKind kind, int dtype, void* stream) {
+  const int rc = check_step(a, kind);
+  return rc != VD_OK ? rc : launch_step(a, dtype, stream);
 }
 
 }  // namespace
@@ -1342,29 +1375,9 @@ int vd_ddim_step_pred(const void* xt, const void* eps, const void* z, void* x_pr
                       const int64_t* t, const int64_t* t_prev, const float* acp, float eta,
                       int clip, int prediction, int64_t B, int64_t per_sample, int dtype,
                       void* stream) {
-  VD_REQUIRE(xt && eps && x_prev && t && t_prev && acp, "null argument");
-  VD_REQUIRE(B > 0 && per_sample > 0, "empty tensor");
-  VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
-  VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
-             prediction);
-  DDIMStep op{acp, t_prev, eta, clip, z != nullptr};
-  const bool v8 = cfg_vec8(per_sample, {xt, eps, z, x_prev, x0});
-  const bool pv = prediction == VD_PRED_V;
-  const int64_t work = B * per_sample / (v8 ? 8 : 1);
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8 && !pv)
-      ddim_kernel<T, 8, false><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
-          op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
-    else if (!pv)
-      ddim_kernel<T, 1, false><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
-          op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
-    else if (v8)
-      ddim_kernel<T, 8, true><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
-          op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
-    else
-      ddim_kernel<T, 1, true><<<grid_for(work), kBlock, 0, VD_STREAM(stream)>>>(
-          op, (const T*)xt, (const T*)eps, (const T*)z, (T*)x_prev, (T*)x0, t, B, per_sample);
-  });
+  return run_step(ddim_args(xt, eps, nullptr, z, x_prev, nullptr, x0, t, t_prev, acp, eta, clip,
+                            prediction, B, per_sample),
+                  STEP_PLAIN, dtype, stream);
 }
 
 int vd_ddim_step(const void* xt, const void* eps, const void* z, void* x_prev, void* x0,
@@ -1410,39 +1423,10 @@ int vd_ddim_step_cfg_pred(const void* xt, const void* eps_c, const void* eps_u, 
                           const int64_t* t_prev, const float* acp, float w, float rescale,
                           const void* workspace, float eta, int clip, int prediction,
                           int64_t B, int64_t per_sample, int dtype, void* stream) {
-  VD_REQUIRE(xt && eps_c && eps_u && x_prev && t && t_prev && acp, "null argument");
-  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
-             (long long)B, (long long)per_sample);
-  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
-  VD_REQUIRE(rescale == 0.f || workspace, "rescale > 0 needs the vd_cfg_stats workspace (null)");
-  VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
-  VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
-             prediction);
-  DDIMStep op{acp, t_prev, eta, clip, z != nullptr};
-  const CfgGuide gd{w};
-  const int nb = cfg_blocks(per_sample);
-  const float* part = static_cast<const float*>(workspace);
-  hipStream_t st = VD_STREAM(stream);
-  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0});
-  const bool pv = prediction == VD_PRED_V;
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8 && !pv)
-      cfg_ddim_kernel<T, 8, false><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
-    else if (!pv)
-      cfg_ddim_kernel<T, 1, false><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
-    else if (v8)
-      cfg_ddim_kernel<T, 8, true><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
-    else
-      cfg_ddim_kernel<T, 1, true><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, per_sample);
-  });
+  return run_step(guided(ddim_args(xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0, t, t_prev, acp,
+                                   eta, clip, prediction, B, per_sample),
+                         w, rescale, workspace, nullptr),
+                  STEP_CFG, dtype, stream);
 }
 
 int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const void* z,
@@ -1458,49 +1442,19 @@ int vd_ddim_step_cfg(const void* xt, const void* eps_c, const void* eps_u, const
 int vd_dpm_step(const void* xt, const void* eps, void* x_prev, void* x0_hist, const float* coef,
                 int64_t n_steps, const int64_t* step, int clip, int64_t B, int64_t per_sample,
                 int dtype, void* stream) {
-  VD_REQUIRE(xt && eps && x_prev && x0_hist && coef && step, "null argument");
-  VD_REQUIRE(B > 0 && per_sample > 0 && n_steps > 0,
-             "empty tensor or table (B=%lld, per_sample=%lld, n_steps=%lld)", (long long)B,
-             (long long)per_sample, (long long)n_steps);
-  DPMStep op{coef, n_steps, step, clip};
-  const bool v8 = cfg_vec8(per_sample, {xt, eps, x_prev, x0_hist});
-  const int64_t n = B * per_sample;
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8)
-      dpm_kernel<T, 8><<<grid_for(n / 8), kBlock, 0, VD_STREAM(stream)>>>(
-          op, (const T*)xt, (const T*)eps, (T*)x_prev, (T*)x0_hist, n);
-    else
-      dpm_kernel<T, 1><<<grid_for(n), kBlock, 0, VD_STREAM(stream)>>>(
-          op, (const T*)xt, (const T*)eps, (T*)x_prev, (T*)x0_hist, n);
-  });
+  return run_step(dpm_args(xt, eps, nullptr, x_prev, nullptr, x0_hist, coef, n_steps, step, clip,
+                           B, per_sample),
+                  STEP_PLAIN, dtype, stream);
 }
 
 int vd_dpm_step_cfg(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
                     void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
                     const int64_t* step, float w, float rescale, const void* workspace, int clip,
                     int64_t B, int64_t per_sample, int dtype, void* stream) {
-  VD_REQUIRE(xt && eps_c && eps_u && x_prev && x0_hist && coef && step, "null argument");
-  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && n_steps > 0,
-             "bad shape (B=%lld, per_sample=%lld, n_steps=%lld)", (long long)B,
-             (long long)per_sample, (long long)n_steps);
-  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
-  VD_REQUIRE(rescale == 0.f || workspace, "rescale > 0 needs the vd_cfg_stats workspace (null)");
-  DPMStep op{coef, n_steps, step, clip};
-  const CfgGuide gd{w};
-  const int nb = cfg_blocks(per_sample);
-  const float* part = static_cast<const float*>(workspace);
-  hipStream_t st = VD_STREAM(stream);
-  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist});
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8)
-      cfg_dpm_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
-          (T*)x0_hist, part, nb, rescale, per_sample);
-    else
-      cfg_dpm_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
-          (T*)x0_hist, part, nb, rescale, per_sample);
-  });
+  return run_step(guided(dpm_args(xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist, coef, n_steps,
+                                  step, clip, B, per_sample),
+                         w, rescale, workspace, nullptr),
+                  STEP_CFG, dtype, stream);
 }
 
 size_t vd_x0_quantile_workspace_size(int64_t B, int64_t per_sample) {
@@ -1530,12 +1484,11 @@ int vd_x0_abs_quantile(const vd_x0_source* src, int64_t rank, float floor, float
     VD_REQUIRE(src->prediction == VD_PRED_EPS || src->prediction == VD_PRED_V,
                "unknown prediction type %d", src->prediction);
     xs.pred_v = src->prediction == VD_PRED_V;
-    xs.ddim = DDIMStep{src->acp, nullptr, 0.f, 0, 0};
-    xs.t = src->t;
+    xs.ddim = make_ddim(src->acp, src->t, nullptr, 0.f, false);
   } else if (src->rule == VD_X0_DPM) {
     VD_REQUIRE(src->eps && src->coef && src->step && src->n_steps > 0,
                "DPM source: null eps, coef or step, or an empty table");
-    xs.dpm = DPMStep{src->coef, src->n_steps, src->step, 0};
+    xs.dpm = make_dpm(src->coef, src->n_steps, src->step);
   } else {
     return vd::fail(VD_EINVAL, "unknown x0 rule %d", src->rule);
   }
@@ -1578,40 +1531,10 @@ int vd_ddim_step_thr(const void* xt, const void* eps_c, const void* eps_u, const
                      const int64_t* t_prev, const float* acp, float w, float rescale,
                      const void* workspace, float eta, int prediction, const float* thresh,
                      int64_t B, int64_t per_sample, int dtype, void* stream) {
-  VD_REQUIRE(xt && eps_c && x_prev && t && t_prev && acp && thresh, "null argument");
-  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0, "bad shape (B=%lld, per_sample=%lld)",
-             (long long)B, (long long)per_sample);
-  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
-  VD_REQUIRE(!eps_u || rescale == 0.f || workspace,
-             "rescale > 0 needs the vd_cfg_stats workspace (null)");
-  VD_REQUIRE(eta == 0.f || z, "eta > 0 needs z");
-  VD_REQUIRE(prediction == VD_PRED_EPS || prediction == VD_PRED_V, "unknown prediction type %d",
-             prediction);
-  DDIMStep op{acp, t_prev, eta, 0, z != nullptr};
-  const CfgGuide gd{w};
-  const int nb = cfg_blocks(per_sample);
-  const float* part = static_cast<const float*>(workspace);
-  hipStream_t st = VD_STREAM(stream);
-  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0});
-  const bool pv = prediction == VD_PRED_V;
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8 && !pv)
-      thr_ddim_kernel<T, 8, false><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
-    else if (!pv)
-      thr_ddim_kernel<T, 1, false><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
-    else if (v8)
-      thr_ddim_kernel<T, 8, true><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
-    else
-      thr_ddim_kernel<T, 1, true><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (const T*)z, (T*)x_prev,
-          (T*)x_prev_dup, (T*)x0, t, part, nb, rescale, thresh, per_sample);
-  });
+  return run_step(guided(ddim_args(xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0, t, t_prev, acp,
+                                   eta, 0, prediction, B, per_sample),
+                         w, rescale, workspace, thresh),
+                  STEP_THR, dtype, stream);
 }
 
 int vd_dpm_step_thr(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
@@ -1619,29 +1542,10 @@ int vd_dpm_step_thr(const void* xt, const void* eps_c, const void* eps_u, void* 
                     const int64_t* step, float w, float rescale, const void* workspace,
                     const float* thresh, int64_t B, int64_t per_sample, int dtype,
                     void* stream) {
-  VD_REQUIRE(xt && eps_c && x_prev && x0_hist && coef && step && thresh, "null argument");
-  VD_REQUIRE(B > 0 && B <= 65535 && per_sample > 0 && n_steps > 0,
-             "bad shape (B=%lld, per_sample=%lld, n_steps=%lld)", (long long)B,
-             (long long)per_sample, (long long)n_steps);
-  VD_REQUIRE(rescale >= 0.f && rescale <= 1.f, "rescale %g outside [0, 1]", (double)rescale);
-  VD_REQUIRE(!eps_u || rescale == 0.f || workspace,
-             "rescale > 0 needs the vd_cfg_stats workspace (null)");
-  DPMStep op{coef, n_steps, step, 0};
-  const CfgGuide gd{w};
-  const int nb = cfg_blocks(per_sample);
-  const float* part = static_cast<const float*>(workspace);
-  hipStream_t st = VD_STREAM(stream);
-  const bool v8 = cfg_vec8(per_sample, {xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist});
-  return VD_DISPATCH_DTYPE(dtype, T, {
-    if (v8)
-      thr_dpm_kernel<T, 8><<<cfg_grid(per_sample, 8, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
-          (T*)x0_hist, part, nb, rescale, thresh, per_sample);
-    else
-      thr_dpm_kernel<T, 1><<<cfg_grid(per_sample, 1, B), kBlock, 0, st>>>(
-          op, gd, (const T*)xt, (const T*)eps_c, (const T*)eps_u, (T*)x_prev, (T*)x_prev_dup,
-          (T*)x0_hist, part, nb, rescale, thresh, per_sample);
-  });
+  return run_step(guided(dpm_args(xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist, coef, n_steps,
+                                  step, 0, B, per_sample),
+                         w, rescale, workspace, thresh),
+                  STEP_THR, dtype, stream);
 }
 
 int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w, float rescale,

@@ -55,7 +55,7 @@ struct Objective {
   int64_t T;
   int min_snr;
   float gamma;
-  // a bad index cannot read out of bounds (as DPMStep::row clamps its own)
+  // a bad index cannot read out of bounds (as DPMRule clamps its own)
   __device__ __forceinline__ int64_t index(int64_t b) const {
     const int64_t i = t[b];
     return i < 0 ? 0 : (i > T - 1 ? T - 1 : i);

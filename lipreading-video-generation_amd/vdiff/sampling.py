@@ -373,8 +373,9 @@ def sample_long(model, sampler, cond, audio, shape, window, stride=None, blend="
     WindowPlan(L, window, stride, blend)) are denoised as one batched forward -- at most
     `window_batch` windows at a time; None: all of them -- their predictions are blended where
     they overlap with the plan's fixed weights, and the long latent is stepped once by the
-    sampler's own kernel, so guidance, its std-rescale over the whole clip, v-prediction and
-    the DPM-Solver++ history work as they do for a short clip.  The audio is encoded once for
+    sampler's rule in the step kernel, so guidance, its std-rescale over the whole clip,
+    v-prediction and the DPM-Solver++ history work as they do for a short clip.  The audio is
+    encoded once for
     the L frames and routed to the windows before the loop.  On a GPU one step is captured and
     replayed (LongDDIMGraph / LongDPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which
     launches the same kernels on the same operands).  L == window is one window: sample_ddim /

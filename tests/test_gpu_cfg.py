@@ -136,13 +136,13 @@ def test_fused_step_exactness(B, P, bf16):
     xp, x0 = ops.ddim_step_cfg(alias, c_d, u_d, t_d, tp_d, acp_d, 2.5, 0.7, out=alias, **kw)
     assert torch.equal(alias, a[0]) and torch.equal(x0, a[1])
     # cond == uncond without rescale: the unguided step, whatever the weight.  g = u exactly
-    # and both kernels inline the same DDIMStep::run, so the bits agree wherever the compiler
-    # fuses the same products.  It does on the 8-wide path, the one every sample shape takes
-    # (3 T H W elements).  vd_ddim_step's scalar instantiation alone evaluates sqrt(a_p) x0 +
-    # dir eps as two rounded products and an add (a packed multiply) where every other
-    # instantiation, its own 8-wide one included, fuses one product: a last-bit difference
-    # that only explicit rounding inside DDIMStep::run, a change of the existing kernel, could
-    # remove.  On that path the two results are held to the fp64 bound of each instead, and to
+    # and both are instantiations of the one step kernel with the same rule, so the bits agree
+    # wherever the compiler fuses the same products.  It does on the 8-wide path, the one every
+    # sample shape takes (3 T H W elements).  On the scalar path nothing but the compiler's
+    # choice keeps two instantiations alike -- vd_ddim_step's scalar one used to evaluate
+    # sqrt(a_p) x0 + dir eps as two rounded products and an add (a packed multiply) where every
+    # other one fuses one product, a last-bit difference that only explicit rounding inside
+    # the rule could exclude.  There the two results are held to the fp64 bound of each, and to
     # each other: one more rounding of a product, and the (at most two) later roundings of
     # x_prev landing differently, each at most u32 mag: 3 u32 mag in fp32, plus for a bf16
     # output the one ulp by which such a difference can move the final rounding.  (One ulp of

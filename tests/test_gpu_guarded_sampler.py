@@ -20,6 +20,11 @@ element at the 8-wide shape: the same values, no store past the tensor.
 Largest error / bound measured on an MI355X, bf16 | fp32: DDIM 0.994 | 0.26, guidance 0.996 | 0.13,
 DPM-Solver++ 0.995 | 0.19 -- the figures of the unguarded tests of the same cases (a bf16 figure is
 the output's own rounding).
+
+What the three shapes do not reach in the step kernel has tests of its own: a sample one
+element-block longer than a full grid of 4096 blocks covers (the grid-stride loop), and 65537
+samples, two more than a grid has rows (the second layer of rows); measured: grid stride 0.996 |
+0.22, sample stride 0.996 | 0.42.
 """
 import math
 
@@ -34,6 +39,7 @@ from oracle.fixtures import seeded
 import _cfg_cases as cfg
 import _dpm_cases as dpm
 import _objective_cases as obj
+import _thr_cases as thr
 from _bounds import assert_elementwise
 from _guarded import Guarded, assert_clean, assert_finite
 
@@ -321,6 +327,170 @@ def test_guarded_dpm(B, P, off, dtype):
                 assert torch.equal(DUP.value(), XP.value()), wh
     print(f"guarded dpm {dtype} B={B} P={P} off={off}: largest error / bound {worst:.3g}")
     record_metric(test="guarded_dpm", B=B, P=P, off=off, dtype=str(dtype), worst=worst)
+
+
+# ------------------------------------------------------------------ the step kernel's two loops
+# one element-block past the cap of 4096 blocks x 256 lanes on the elements of a sample: odd, so
+# the scalar path, whose blocks take a second trip
+P_STRIDE = 4096 * 256 + 257
+# one sample past the 65535 rows of a grid: the plain entry points stride the samples over the
+# rows, the guided and thresholded ones refuse
+B_ROWS = 65537
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rule", ["ddim-eps", "dpm"])
+def test_guarded_step_grid_stride(rule, dtype):
+    """The grid-stride loop within a sample: B = 2, P = P_STRIDE, on the plain, the guided (7.5,
+    0.7) and the thresholded guided step of DDIM-eps and of DPM-Solver++ on its middle row.
+    Outputs fully written, guards intact, inputs unchanged, values inside the fp64 bounds of
+    _cfg_cases / _dpm_cases (the thresholded ones through _thr_cases, whose quantile lies above
+    the floor 1 in both samples, so the threshold is no clamp to [-1, 1])."""
+    from vdiff import _lib
+    bf = dtype == torch.bfloat16
+    B, P = 2, P_STRIDE
+    assert P % 8 and P > 4096 * 256
+    DT = _dt(dtype)
+    w, phi = thr.W, 0.7
+    xt, c, u, other = cfg.inputs(B, P, bf)   # other: z, or the x0 history
+    XT, C, U, O = (_in(xt, dtype, "xt"), _in(c, dtype, "eps_c"), _in(u, dtype, "eps_u"),
+                   _in(other, dtype, "z / x0_last"))
+    if rule == "dpm":
+        s = thr.dpm_sampler()
+        row, n = dpm.kernel_rows(s)[1], s.steps
+        assert s.coef[row, 4] != 0
+        COEF, STEP = _tab(s.coef, "coef"), _tab(torch.tensor([row]), "step")
+        tabs, kw = [COEF, STEP], dict(row=s.coef[row])
+        src_kw = dict(coef=COEF.p, step=STEP.p, n_steps=n, rule=_lib.X0_DPM)
+    else:
+        t, tp = cfg.timesteps(B)
+        acp = dpm.schedules()["v2"]
+        Tt, Tp, ACP = _tab(t, "t"), _tab(tp, "t_prev"), _tab(acp, "acp")
+        tabs, kw = [Tt, Tp, ACP], dict(t=t, tp=tp, acp=acp, eta=0.5)
+        src_kw = dict(t=Tt.p, acp=ACP.p, rule=_lib.X0_DDIM, prediction=0)
+    WS = _stats(C, U, w, B, P, DT, f"{rule} {dtype} grid stride")
+    worst = 0.0
+    for path in ("plain", "guided", "thresholded"):
+        what = f"grid stride {rule} {path} {dtype}"
+        guide = None if path == "plain" else (w, phi)
+        base, K = thr.base64(rule, xt, c, u, other, guide, **kw)
+        ins = [XT, C] + tabs + ([] if path == "plain" else [U, WS])
+        XP = _out((B, P), dtype, "x_prev")
+        DUP = None if path == "plain" else _out((B, P), dtype, "x_prev_dup")
+        # DPM: the history, read and written in place
+        X0 = _in(other, dtype, "x0_hist") if rule == "dpm" else _out((B, P), dtype, "x0")
+        if path == "thresholded":
+            ref = thr.thresholded(base, K)
+            assert bool((ref["q"] > 1).all()), ref["q"]
+            nws = _lib.lib().vd_x0_quantile_workspace_size(B, P)
+            QWS = Guarded.workspace(nws, dev, name="select workspace")
+            S = _out((B,), f32, "s")
+            src = _lib.X0Source(x=XT.p, eps=C.p, eps_u=U.p, cfg_workspace=WS.ptr, w=w, rescale=phi,
+                                **src_kw)
+            _lib.call("vd_x0_abs_quantile", src, thr.rank(thr.P_THR, P), 1.0, math.inf, B, P, DT,
+                      S.p, QWS.ptr, nws, _st())
+            assert_clean([S], ins, [QWS], what=what + " select")
+            s_ref, Delta = ref["s"]
+            assert ((S.value().double().view(-1, 1) - s_ref).abs() <= Delta).all(), what
+            ins.append(S.freeze())
+            if rule == "dpm":
+                _lib.call("vd_dpm_step_thr", XT.p, C.p, U.p, XP.p, DUP.p, X0.p, COEF.p, n, STEP.p,
+                          w, phi, WS.ptr, S.p, B, P, DT, _st())
+            else:
+                _lib.call("vd_ddim_step_thr", XT.p, C.p, U.p, O.p, XP.p, DUP.p, X0.p, Tt.p, Tp.p,
+                          ACP.p, w, phi, WS.ptr, 0.5, 0, S.p, B, P, DT, _st())
+        else:
+            ref = base
+            guided = [] if path == "plain" else [w, phi, WS.ptr]
+            mid = [] if path == "plain" else [U.p]
+            dupl = [] if path == "plain" else [DUP.p]
+            if rule == "dpm":
+                _lib.call("vd_dpm_step" if path == "plain" else "vd_dpm_step_cfg", XT.p, C.p, *mid,
+                          XP.p, *dupl, X0.p, COEF.p, n, STEP.p, *guided, 0, B, P, DT, _st())
+            else:
+                _lib.call("vd_ddim_step" if path == "plain" else "vd_ddim_step_cfg", XT.p, C.p,
+                          *mid, O.p, XP.p, *dupl, X0.p, Tt.p, Tp.p, ACP.p, *guided, 0.5, 0, B, P,
+                          DT, _st())
+        if rule == "dpm":
+            assert_clean([g for g in (XP, DUP) if g], ins, what=what, inouts=[X0])
+        else:
+            assert_clean([g for g in (XP, DUP, X0) if g], ins + [O], what=what)
+        assert_finite([XP, X0], what=what)
+        worst = max(worst, _check(XP.value(), ref, "x_prev", bf, what),
+                    _check(X0.value(), ref, "x0", bf, what))
+        if DUP:
+            assert torch.equal(DUP.value(), XP.value()), what
+    print(f"guarded grid stride {rule} {dtype}: largest error / bound {worst:.3g}")
+    record_metric(test="guarded_step_grid_stride", rule=rule, dtype=str(dtype), worst=worst)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("P", [1, 8])
+def test_guarded_step_sample_stride(P, dtype):
+    """More samples than a grid has rows, B = B_ROWS, one element and one 8-vector each:
+    vd_ddim_step, vd_ddim_step_pred on v and vd_dpm_step (the middle row) stride the samples.  t
+    cycles over the whole table, 0 and T - 1 included, with t_prev = -1 below t = 10.  Outputs
+    fully written, guards intact, inputs unchanged, values inside the fp64 bounds.  The guided
+    and the thresholded entry points refuse this B with VD_EINVAL and launch nothing: their
+    outputs keep the pattern."""
+    from vdiff import _lib
+    bf = dtype == torch.bfloat16
+    B = B_ROWS
+    DT = _dt(dtype)
+    xt, c, u, other = cfg.inputs(B, P, bf)
+    acp = dpm.schedules()["v2"]
+    T = acp.numel()
+    t = torch.arange(B) % T
+    tp = torch.where(t >= 10, t - 10, torch.full_like(t, -1))
+    assert 0 in t.tolist() and T - 1 in t.tolist() and -1 in tp.tolist()
+    s = thr.dpm_sampler()
+    row, n = dpm.kernel_rows(s)[1], s.steps
+    XT, C, O = _in(xt, dtype, "xt"), _in(c, dtype, "eps"), _in(other, dtype, "z / x0_last")
+    Tt, Tp, ACP = _tab(t, "t"), _tab(tp, "t_prev"), _tab(acp, "acp")
+    COEF, STEP = _tab(s.coef, "coef"), _tab(torch.tensor([row]), "step")
+    worst = 0.0
+    for fn, pred in (("vd_ddim_step", "eps"), ("vd_ddim_step_pred", "v")):
+        what = f"sample stride {fn} {pred} {dtype} P={P}"
+        XP, X0 = _out((B, P), dtype, "x_prev"), _out((B, P), dtype, "x0")
+        args = [XT.p, C.p, O.p, XP.p, X0.p, Tt.p, Tp.p, ACP.p, 0.5, 1]
+        if fn == "vd_ddim_step_pred":
+            args.append(_lib.PREDICTIONS[pred])
+        _lib.call(fn, *args, B, P, DT, _st())
+        assert_clean([XP, X0], [XT, C, O, Tt, Tp, ACP], what=what)
+        if pred == "v":
+            ref = obj.ddim_ref64(xt, c, c, other, t, tp, acp, 0.0, 0.0, 0.5, True, False)
+        else:
+            ref = cfg.ref64(xt, c, c, other, t, tp, acp, 0.0, 0.0, 0.5, True)
+        worst = max(worst, _check(XP.value(), ref, "x_prev", bf, what),
+                    _check(X0.value(), ref, "x0", bf, what))
+    what = f"sample stride vd_dpm_step {dtype} P={P}"
+    XP, H = _out((B, P), dtype, "x_prev"), _in(other, dtype, "x0_hist")
+    _lib.call("vd_dpm_step", XT.p, C.p, XP.p, H.p, COEF.p, n, STEP.p, 0, B, P, DT, _st())
+    assert_clean([XP], [XT, C, COEF, STEP], what=what, inouts=[H])
+    ref = dpm.ref64(xt, c, other, s.coef[row], False)
+    worst = max(worst, _check(XP.value(), ref, "x_prev", bf, what),
+                _check(H.value(), ref, "x0", bf, what))
+    # B > 65535 on a per-sample-only entry point: VD_EINVAL (1) before anything is launched
+    U = _in(u, dtype, "eps_u")
+    S = _in(torch.ones(B), f32, "s")
+    XP, DUP, X0 = (_out((B, P), dtype, n_) for n_ in ("x_prev", "x_prev_dup", "x0"))
+    H = _in(other, dtype, "x0_hist")
+    lib = _lib.lib()
+    w = thr.W
+    for rc in (lib.vd_ddim_step_cfg(XT.p, C.p, U.p, O.p, XP.p, DUP.p, X0.p, Tt.p, Tp.p, ACP.p, w,
+                                    0.0, None, 0.5, 1, B, P, DT, _st()),
+               lib.vd_dpm_step_cfg(XT.p, C.p, U.p, XP.p, DUP.p, H.p, COEF.p, n, STEP.p, w, 0.0,
+                                   None, 0, B, P, DT, _st()),
+               lib.vd_ddim_step_thr(XT.p, C.p, U.p, O.p, XP.p, DUP.p, X0.p, Tt.p, Tp.p, ACP.p, w,
+                                    0.0, None, 0.5, 0, S.p, B, P, DT, _st()),
+               lib.vd_dpm_step_thr(XT.p, C.p, U.p, XP.p, DUP.p, H.p, COEF.p, n, STEP.p, w, 0.0,
+                                   None, S.p, B, P, DT, _st())):
+        assert rc == 1 and b"bad shape" in lib.vd_last_error()
+    assert_clean([], [XT, C, U, O, Tt, Tp, ACP, COEF, STEP, S, H], what="refused B")
+    for g in (XP, DUP, X0):
+        assert bool(g.unwritten().all()) and g.guards_intact(), g.name
+    print(f"guarded sample stride {dtype} P={P}: largest error / bound {worst:.3g}")
+    record_metric(test="guarded_step_sample_stride", P=P, dtype=str(dtype), worst=worst)
 
 
 # ------------------------------------------------------------------ timestep embedding

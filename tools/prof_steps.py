@@ -1,7 +1,7 @@
 """Per-step kernel time by category from a rocprofv3 --kernel-trace database of a bench run:
 steps are cut at each q_sample launch (one per train step); prints the categories of the
 last steps (the timed ones) in ms per step.   python tools/prof_steps.py run_results.db [cut]
-cut: a kernel-name substring that starts each step (default QSample; ddim_kernel for DDIM).
+cut: a kernel-name substring that starts each step (default QSample; step_kernel for DDIM).
 Also prints the per-kernel table (name, launches, ms) of the last step."""
 import sqlite3
 import sys
