@@ -64,11 +64,11 @@ int vd_timestep_embedding_tab(const int64_t* t, int B, int dim, const float* fre
  * Alignment of the per-sample kernels -- ONE rule for every entry point of this group:
  * vd_q_sample, vd_p_sample_v1 / _v2 / _cosine, vd_ddim_step / _pred, vd_cfg_stats,
  * vd_cfg_combine, vd_ddim_step_cfg / _cfg_pred, vd_dpm_step / _cfg, vd_x0_abs_quantile,
- * vd_ddim_step_thr, vd_dpm_step_thr.  A call moves 8 elements
- * per lane (16-byte accesses) when per_sample % 8 == 0 AND every non-null tensor pointer it is
- * given (inputs, outputs, the duplicate, the history) is 16-byte aligned; any other call runs
- * one element at a time, so element-aligned pointers are always legal.  Both paths perform the
- * same fp32 operations per element.  Tables, t / t_prev / step and the statistics workspace
+ * vd_ddim_step_thr, vd_dpm_step_thr, vd_ddim_step_known, vd_dpm_step_known.  A call moves 8
+ * elements per lane (16-byte accesses) when per_sample % 8 == 0 AND every non-null tensor
+ * pointer it is given (inputs, outputs, the duplicate, the history) is 16-byte aligned; any
+ * other call runs one element at a time, so element-aligned pointers are always legal.  Both
+ * paths perform the same fp32 operations per element.  Tables, t / t_prev / step and the statistics workspace
  * need their natural alignment only.  (vd_mse_loss / _bwd, below, are stricter: they refuse
  * unaligned tensors with VD_EINVAL.)
  *
@@ -314,6 +314,48 @@ int vd_dpm_step_thr(const void* xt, const void* eps_c, const void* eps_u, void* 
                     void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
                     const int64_t* step, float w, float rescale, const void* workspace,
                     const float* thresh, int64_t B, int64_t per_sample, int dtype, void* stream);
+
+/* ---- masked sampling: known pixels and frames kept inside the step (inpainting, clip
+ * continuation; build extension, no reference counterpart) ----
+ * known: the clip to keep, [B][per_sample] in `dtype` like xt.  keep: fp32 [Bk][S], Bk in {1, B},
+ * S > 0 a divisor of per_sample (the product of the spatial dimensions): element i of sample b
+ * reads k = keep[Bk == 1 ? 0 : b][i % S], so a row is broadcast over the channels and, Bk == 1,
+ * over the batch; k <= 0 is read as 0 and k >= 1 as 1.  Per element, in fp32, with y the x0 the
+ * step forms today (rule -> static clamp or dynamic threshold) and e the model's direction term:
+ *   k == 0:  x0' = y,                     e' = e         (today's expressions and bits)
+ *   k == 1:  x0' = x_k,                   e' = e_k       (selects: a non-finite model output
+ *                                                         there reaches no output)
+ *   else:    x0' = (1 - k) y + k x_k,     e' = (1 - k) e + k e_k
+ *   e_k = (xt - sqrt(a_t) x_k) / sqrt(1 - a_t)           (DDIM; 2M has no direction term)
+ *   x_prev = the rule's x_prev on (xt, x0', e', z | x0_last), unchanged.
+ * x0' goes to x_prev, x_prev_dup, x0 and the 2M history; x_k is never clamped or divided by the
+ * threshold.  With eta = 0 an element with k == 1 therefore stays on the line x_k and xt span,
+ * whatever the model says: DDIM x_prev = sqrt(a_p) x_k + dir e_k; 2M x_prev = A xt + (B + C) x_k
+ * once the history holds x_k; the last step returns x_k itself.
+ * vd_ddim_step_known: vd_ddim_step_pred, _cfg_pred and _thr in one: eps_u == NULL is the
+ * unguided step on eps_c (w, rescale, workspace not read; any B), otherwise B <= 65535; thresh
+ * != NULL is the thresholded step (clip must be 0).  vd_dpm_step_known: vd_dpm_step, _cfg and
+ * _thr the same way.  known == keep == NULL: the unmasked step; one of them alone is refused.
+ * Alignment: the rule above over known and keep too, so that a masked step runs 8-wide exactly
+ * where the unmasked step on the same tensors does (the k == 0 bits are the unmasked step's at
+ * the same width).  The mask index is computed once per vector; with S % 8 == 0 a vector lies
+ * inside one channel of the mask and its mask values are one vector load, otherwise they are
+ * read one element at a time, so no access straddles the end of a mask row.
+ * known and keep are read only and may alias no output; x_prev may alias xt and the
+ * history is in place, as in the unmasked steps.  Plain vector loads and stores: no atomics, no
+ * workspace, no memset. */
+int vd_ddim_step_known(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                       void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                       const int64_t* t_prev, const float* acp, float w, float rescale,
+                       const void* workspace, float eta, int clip, int prediction,
+                       const float* thresh, const void* known, const float* keep, int64_t Bk,
+                       int64_t S, int64_t B, int64_t per_sample, int dtype, void* stream);
+int vd_dpm_step_known(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
+                      void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
+                      const int64_t* step, float w, float rescale, const void* workspace,
+                      int clip, const float* thresh, const void* known, const float* keep,
+                      int64_t Bk, int64_t S, int64_t B, int64_t per_sample, int dtype,
+                      void* stream);
 
 /* Long-clip sampling (build extension, no reference counterpart): a latent of L frames is
  * denoised as W overlapping windows of T frames, one batched forward per step, and the windows'

@@ -508,6 +508,10 @@ struct DDIMScalars {
     sq_ap = sqrtf(ap);
   }
   __device__ __forceinline__ bool third() const { return has_z; }
+  // e_k: the direction a perfect denoiser would give at a known x0 (masked step)
+  __device__ __forceinline__ float direction_known(float xt, float xk) const {
+    return (xt - sq_at * xk) / sq_1mat;
+  }
   __device__ __forceinline__ float x_prev(float, float x0, float e, float z) const {
     float v = sq_ap * x0 + dir * e;
     if (has_z) v += sigma * z;
@@ -552,6 +556,7 @@ struct DPMRule {
   __device__ __forceinline__ bool third() const { return C != 0.f; }
   __device__ __forceinline__ float x0(float xt, float m) const { return (xt - sigma * m) / alpha; }
   __device__ __forceinline__ float direction(float, float m) const { return m; }
+  __device__ __forceinline__ float direction_known(float, float) const { return 0.f; }  // unused
   __device__ __forceinline__ float x_prev(float xt, float x0, float, float last) const {
     float v = A * xt + B * x0;
     if (C != 0.f) v += C * last;
@@ -568,11 +573,42 @@ struct DPMRule {
 // Aliasing: x_prev may be xt, and the DPM history arrives as both `third` and `x0o`, read and
 // written in place: a lane reads its elements before it writes them and no other lane touches
 // them, so xt, third, xprev, xdup and x0o carry no __restrict__.
-template <typename T, int VEC, typename Rule, bool THR, bool GUIDED>
+//
+// KNOWN (masked sampling): after the clamp or the threshold, x0 is replaced by the known clip
+// x_k where keep says so.  keep is fp32 [Bk][S], Bk in {1, B}, S a divisor of per_sample: element
+// i of a sample reads keep[i % S], so one mask row serves every channel (and, Bk = 1, every
+// sample).  k <= 0: x0 and the direction term are the model's, the expressions and bits of the
+// unmasked step; k >= 1: x0 = x_k and the direction becomes the rule's direction_known -- both
+// selects, so a non-finite model output there reaches no output; in between both are blended,
+// (1 - k) y + k x_k.  x_k is never clamped or divided by the threshold.  The step runs 8-wide
+// exactly where the unmasked step does (cfg_vec8, known and keep among the pointers): its k <= 0
+// bits are the unmasked kernel's only at the same width, whose instantiations do not all fuse the
+// same products.  The mask index is one remainder per vector; with S % 8 == 0 the vector lies
+// inside one channel and its eight mask values are one vector load, otherwise they are read one
+// element at a time.
+// known and keep are inputs only and alias no output.  KNOWN = false: `kn` is empty and unread.
+// Every vector is first stepped and stored unmasked; one that holds a kept element is then
+// formed again and stored over it (the comment in the kernel says why).
+__device__ __forceinline__ float opaque(float v) {
+  asm volatile("" : "+v"(v));  // no instruction: the value, as one the optimiser knows nothing of
+  return v;
+}
+
+template <typename T, bool KNOWN>
+struct KnownOps {};
+template <typename T>
+struct KnownOps<T, true> {
+  const T* known;
+  const float* keep;
+  int64_t S, row;  // row: keep's sample stride, 0 (Bk = 1) or S
+};
+
+template <typename T, int VEC, typename Rule, bool THR, bool GUIDED, bool KNOWN>
 __global__ void __launch_bounds__(kBlock) step_kernel(
     Rule rule, CfgGuide gd, const T* xt, const T* __restrict__ c, const T* __restrict__ u,
     const T* third, T* xprev, T* xdup, T* x0o, const float* __restrict__ part, int nb, float phi,
-    const float* __restrict__ thr, int clip, int64_t B, int64_t per_sample) {
+    const float* __restrict__ thr, int clip, int64_t B, int64_t per_sample,
+    KnownOps<T, KNOWN> kn) {
   // The sample: the row, strided over the grid's rows by the layer (cfg_grid).  A row past B (the
   // last layer's) takes the last sample's scalars and an empty range: an early return would hold
   // every other argument's load back behind B's.
@@ -593,6 +629,28 @@ __global__ void __launch_bounds__(kBlock) step_kernel(
     ld_vec(xt + e, xa, VEC);
     model_out<T, VEC>(c + e, GUIDED ? u + e : nullptr, GUIDED, gd, f, scale, m);
     if (has3) ld_vec(third + e, x3, VEC);
+    [[maybe_unused]] float xk[8], kp[8];
+    if constexpr (KNOWN) {
+      // the vector's place in the mask row: one remainder per vector (32-bit where it fits)
+      const int64_t i0 = v * VEC;
+      const int64_t sp = per_sample <= 0xffffffffll
+                             ? (int64_t)((uint32_t)i0 % (uint32_t)kn.S)
+                             : i0 % kn.S;
+      ld_vec(kn.known + e, xk, VEC);
+      const float* krow = kn.keep + b * kn.row;
+      if (VEC == 1 || kn.S % VEC == 0) {
+        ld_vec(krow + sp, kp, VEC);  // the vector lies inside one channel of the mask
+      } else {
+        // it may cross into the next channel: its mask values one element at a time, the index
+        // stepped and wrapped, so that no access straddles the end of the mask row
+        int64_t j = sp;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+          kp[i] = krow[j];
+          if (++j == kn.S) j = 0;
+        }
+      }
+    }
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       float x0 = rule.x0(xa[i], m[i]);
@@ -604,6 +662,38 @@ __global__ void __launch_bounds__(kBlock) step_kernel(
     st_vec(xprev + e, y0, VEC);
     if (xdup) st_vec(xdup + e, y0, VEC);
     if (x0o) st_vec(x0o + e, y1, VEC);
+    if constexpr (KNOWN) {
+      // Up to here the vector went through the unmasked step, statement for statement, stores
+      // included: that is what gives k <= 0 the unmasked kernel's bits.  (Formed in one block
+      // with the masked values, or from selected operands, the sums fuse another of their
+      // products into the multiply-add and the last bit moves.)  A vector with a kept element
+      // is formed again from copies of the operands that the optimiser cannot see through, and
+      // stored over the first result; its k <= 0 elements keep the values of the first pass.
+      bool any = false;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) any |= kp[i] > 0.f;
+      if (any) {
+        float z0[8], z1[8];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+          const float xb = opaque(xa[i]), yb = opaque(y1[i]), pb = opaque(y0[i]);
+          const float lb = opaque(x3[i]);
+          const float db = rule.direction(xb, opaque(m[i]));
+          const float k = kp[i];
+          float xm = xk[i], dm = rule.direction_known(xb, xk[i]);
+          if (k < 1.f) {
+            xm = (1.f - k) * yb + k * xm;
+            dm = (1.f - k) * db + k * dm;
+          }
+          const bool kept = k > 0.f;
+          z1[i] = kept ? xm : yb;
+          z0[i] = kept ? rule.x_prev(xb, xm, dm, lb) : pb;
+        }
+        st_vec(xprev + e, z0, VEC);
+        if (xdup) st_vec(xdup + e, z0, VEC);
+        if (x0o) st_vec(x0o + e, z1, VEC);
+      }
+    }
   }
 }
 
@@ -781,6 +871,9 @@ struct StepArgs {
   const float* thresh = nullptr;
   int clip = 0;
   int64_t B = 0, per_sample = 0;
+  const void* known = nullptr;  // masked step: the clip to keep and keep fp32 [Bk][S]
+  const float* keep = nullptr;
+  int64_t Bk = 0, S = 0;
 };
 
 // The one place a rule is built: launch_step and vd_x0_abs_quantile (t_prev NULL: its x0 piece
@@ -822,6 +915,14 @@ int check_step(const StepArgs& a, StepKind kind) {
     VD_REQUIRE(!a.u || a.rescale == 0.f || a.workspace,
                "rescale > 0 needs the vd_cfg_stats workspace (null)");
   }
+  VD_REQUIRE((a.known != nullptr) == (a.keep != nullptr),
+             "known and keep are given together or not at all");
+  if (a.known) {
+    VD_REQUIRE((a.Bk == 1 || a.Bk == a.B) && a.S > 0 && a.per_sample % a.S == 0,
+               "bad keep mask (Bk=%lld for B=%lld, S=%lld for per_sample=%lld)", (long long)a.Bk,
+               (long long)a.B, (long long)a.S, (long long)a.per_sample);
+    VD_REQUIRE(!(a.thresh && a.clip), "thresh and clip exclude each other");
+  }
   if (!dpm) {
     VD_REQUIRE(a.eta == 0.f || a.third, "eta > 0 needs z");
     VD_REQUIRE(a.prediction == VD_PRED_EPS || a.prediction == VD_PRED_V,
@@ -840,23 +941,32 @@ void dispatch_bool(bool v, F&& f) {
 
 template <typename T, typename Rule>
 void launch_rule(const Rule& rule, const StepArgs& a, hipStream_t st) {
-  const bool v8 = cfg_vec8(a.per_sample, {a.xt, a.c, a.u, a.third, a.xprev, a.xdup, a.x0});
+  // masked: the unmasked step's width (its bits where k <= 0), known and keep aligned as well
+  const bool v8 = cfg_vec8(a.per_sample, {a.xt, a.c, a.u, a.third, a.xprev, a.xdup, a.x0, a.known,
+                                          a.keep});
   const dim3 grid = cfg_grid(a.per_sample, v8 ? 8 : 1, a.B);
   dispatch_bool(v8, [&](auto V8) {
     dispatch_bool(a.thresh != nullptr, [&](auto THR) {
       dispatch_bool(a.u != nullptr, [&](auto GUIDED) {
-        step_kernel<T, decltype(V8)::value ? 8 : 1, Rule, decltype(THR)::value,
-                    decltype(GUIDED)::value><<<grid, kBlock, 0, st>>>(
-            rule, CfgGuide{a.w}, (const T*)a.xt, (const T*)a.c, (const T*)a.u, (const T*)a.third,
-            (T*)a.xprev, (T*)a.xdup, (T*)a.x0, static_cast<const float*>(a.workspace),
-            cfg_blocks(a.per_sample), a.rescale, a.thresh, a.clip, a.B, a.per_sample);
+        dispatch_bool(a.known != nullptr, [&](auto KNOWN) {
+          constexpr bool kKnown = decltype(KNOWN)::value;
+          KnownOps<T, kKnown> kn;
+          if constexpr (kKnown)
+            kn = {(const T*)a.known, a.keep, a.S, a.Bk == 1 ? (int64_t)0 : a.S};
+          step_kernel<T, decltype(V8)::value ? 8 : 1, Rule, decltype(THR)::value,
+                      decltype(GUIDED)::value, kKnown><<<grid, kBlock, 0, st>>>(
+              rule, CfgGuide{a.w}, (const T*)a.xt, (const T*)a.c, (const T*)a.u,
+              (const T*)a.third, (T*)a.xprev, (T*)a.xdup, (T*)a.x0,
+              static_cast<const float*>(a.workspace), cfg_blocks(a.per_sample), a.rescale,
+              a.thresh, a.clip, a.B, a.per_sample, kn);
+        });
       });
     });
   });
 }
 
 // Vector width (cfg_vec8 over all non-null pointers), grid, and the dispatch over dtype, rule,
-// threshold, guidance and VEC: one launch line.
+// threshold, guidance, mask and VEC: one launch line.
 int launch_step(const StepArgs& a, int dtype, void* stream) {
   hipStream_t st = VD_STREAM(stream);
   return VD_DISPATCH_DTYPE(dtype, T, {
@@ -903,6 +1013,15 @@ StepArgs dpm_args(const void* xt, const void* c, const void* u, void* x_prev, vo
 StepArgs guided(StepArgs a, float w, float rescale, const void* workspace, const float* thresh) {
   a.w = w, a.rescale = rescale, a.workspace = workspace, a.thresh = thresh;
   return a;
+}
+
+// known / keep of a masked step, and the kind its other operands make it
+StepArgs masked(StepArgs a, const void* known, const float* keep, int64_t Bk, int64_t S) {
+  a.known = known, a.keep = keep, a.Bk = Bk, a.S = S;
+  return a;
+}
+inline StepKind kind_of(const StepArgs& a) {
+  return a.thresh ? STEP_THR : (a.u ? STEP_CFG : STEP_PLAIN);
 }
 
 int run_step(const StepArgs& a, StepKind kind, int dtype, void* stream) {
@@ -1546,6 +1665,32 @@ int vd_dpm_step_thr(const void* xt, const void* eps_c, const void* eps_u, void* 
                                   step, 0, B, per_sample),
                          w, rescale, workspace, thresh),
                   STEP_THR, dtype, stream);
+}
+
+int vd_ddim_step_known(const void* xt, const void* eps_c, const void* eps_u, const void* z,
+                       void* x_prev, void* x_prev_dup, void* x0, const int64_t* t,
+                       const int64_t* t_prev, const float* acp, float w, float rescale,
+                       const void* workspace, float eta, int clip, int prediction,
+                       const float* thresh, const void* known, const float* keep, int64_t Bk,
+                       int64_t S, int64_t B, int64_t per_sample, int dtype, void* stream) {
+  const StepArgs a = masked(guided(ddim_args(xt, eps_c, eps_u, z, x_prev, x_prev_dup, x0, t,
+                                             t_prev, acp, eta, clip, prediction, B, per_sample),
+                                   w, rescale, workspace, thresh),
+                            known, keep, Bk, S);
+  return run_step(a, kind_of(a), dtype, stream);
+}
+
+int vd_dpm_step_known(const void* xt, const void* eps_c, const void* eps_u, void* x_prev,
+                      void* x_prev_dup, void* x0_hist, const float* coef, int64_t n_steps,
+                      const int64_t* step, float w, float rescale, const void* workspace,
+                      int clip, const float* thresh, const void* known, const float* keep,
+                      int64_t Bk, int64_t S, int64_t B, int64_t per_sample, int dtype,
+                      void* stream) {
+  const StepArgs a = masked(guided(dpm_args(xt, eps_c, eps_u, x_prev, x_prev_dup, x0_hist, coef,
+                                            n_steps, step, clip, B, per_sample),
+                                   w, rescale, workspace, thresh),
+                            known, keep, Bk, S);
+  return run_step(a, kind_of(a), dtype, stream);
 }
 
 int vd_cfg_combine(const void* eps_c, const void* eps_u, void* eps_out, float w, float rescale,

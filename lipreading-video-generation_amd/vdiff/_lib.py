@@ -116,6 +116,10 @@ _SIGS = {
                               _i, _vp, _i64, _i64, _i, _vp]),
     "vd_dpm_step_thr": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp,
                              _i64, _i64, _i, _vp]),
+    "vd_ddim_step_known": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _f,
+                                _i, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _vp]),
+    "vd_dpm_step_known": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i, _vp,
+                               _vp, _vp, _i64, _i64, _i64, _i64, _i, _vp]),
     "vd_window_gather": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i, _vp]),
     "vd_window_blend": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i,
                              _vp]),

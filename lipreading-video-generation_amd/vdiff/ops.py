@@ -325,6 +325,11 @@ class _DDIMArgs:
                                     _p(self.t), _p(self.tp), _p(self.acp), a.w, a.phi, a.ws,
                                     self.eta, self.pid, a.s)
 
+    def masked(self, a):
+        return "vd_ddim_step_known", (a.xt, a.c, a.u, _p(self.z), _p(self.xp), a.dup,
+                                      _p(self.x0), _p(self.t), _p(self.tp), _p(self.acp), a.w,
+                                      a.phi, a.ws, self.eta, a.clip, self.pid, a.s, *a.mask)
+
 
 class _DPMArgs:
     """The same for DPM-Solver++(2M): x0_hist / out / dup contiguous buffers like xt, coef the
@@ -356,16 +361,52 @@ class _DPMArgs:
         return "vd_dpm_step_thr", (a.xt, a.c, a.u, _p(self.xp), a.dup, _p(self.x0), _p(self.coef),
                                    self.n, _p(self.step), a.w, a.phi, a.ws, a.s)
 
+    def masked(self, a):
+        return "vd_dpm_step_known", (a.xt, a.c, a.u, _p(self.xp), a.dup, _p(self.x0),
+                                     _p(self.coef), self.n, _p(self.step), a.w, a.phi, a.ws,
+                                     a.clip, a.s, *a.mask)
 
-def _sampler_step(op, rule, rule_args, xt, eps_c, eps_u, scale, rescale, clip, thresh, out, dup):
+
+def _mask_args(op, xt, known, keep):
+    """Checked (known, keep, Bk, S) pointers and sizes of a masked step, or None without a mask.
+    known: the clip to keep, a contiguous tensor of xt's shape and dtype.  keep: contiguous fp32
+    [Bk, S] (or [Bk, 1, *spatial]), Bk in {1, B}, S the product of xt's dimensions past the
+    channels (xt [B, P]: any S that divides P).  Both stay alive until the call returns: the
+    caller holds them."""
+    if known is None and keep is None:
+        return None
+    if known is None or keep is None:
+        raise ValueError(f"{op}: known and keep are given together or not at all")
+    if known.dtype != xt.dtype or known.shape != xt.shape or not known.is_contiguous():
+        raise ValueError(f"{op}: `known` must be a contiguous {xt.dtype} tensor of xt's shape "
+                         f"{tuple(xt.shape)}, got {known.dtype} {tuple(known.shape)}")
+    B = xt.shape[0]
+    P = xt.numel() // max(B, 1)
+    spatial = tuple(xt.shape[2:])
+    if keep.dim() > 2 and tuple(keep.shape[1:]) == (1,) + spatial:
+        keep = keep.view(keep.shape[0], -1) if keep.is_contiguous() else keep
+    S = math.prod(spatial) if xt.dim() > 2 else (keep.shape[1] if keep.dim() == 2 else 0)
+    if keep.dtype != torch.float32 or keep.dim() != 2 or not keep.is_contiguous() \
+            or keep.shape[0] not in (1, B) or keep.shape[1] != S or S < 1 or P % S:
+        raise ValueError(f"{op}: `keep` must be a contiguous fp32 [Bk, S] mask, Bk in (1, {B}), "
+                         f"S = {S if xt.dim() > 2 else 'a divisor of ' + str(P)}, got "
+                         f"{keep.dtype} {tuple(keep.shape)}")
+    _gpu(known, keep)
+    return _p(known), _p(keep), keep.shape[0], S
+
+
+def _sampler_step(op, rule, rule_args, xt, eps_c, eps_u, scale, rescale, clip, thresh, out, dup,
+                  known=None, keep=None):
     """The body of ddim_step, ddim_step_cfg, dpm_step and dpm_step_cfg: (x_prev, x0) of one
     update through the library's step kernel.  eps_u None: unguided (scale 1, rescale 0).
     rule(op, xt, B, out, dup, *rule_args): _DDIMArgs or _DPMArgs.  Library calls, in this order:
     vd_cfg_stats (guided with rescale > 0, in _cfg_args), vd_x0_abs_quantile on the step's own x0
     (thresh), then one step entry point -- the rule's plain or guided one, or its thresholded
-    one, which serves both."""
+    one, which serves both.  known / keep (a masked step, _mask_args): the rule's masked entry
+    point, which serves all three, in the step entry point's place."""
     if thresh is not None:
         _thresh_args(thresh, clip)
+    mask = _mask_args(op, xt, known, keep)
     _gpu(xt, eps_c, out, dup)
     xt = _flat(xt)
     if eps_u is None:
@@ -387,22 +428,31 @@ def _sampler_step(op, rule, rule_args, xt, eps_c, eps_u, scale, rescale, clip, t
         entry, args = r.thresholded(a)
     else:
         entry, args = r.plain(a) if eps_u is None else r.guided(a)
+    if mask is not None:
+        a.mask = mask
+        entry, args = r.masked(a)
     _lib.call(entry, *args, B, P, _dtype(xt), _stream(xt))
     return r.xp, r.x0
 
 
 def ddim_step(xt, eps, t, t_prev, acp, eta=0.0, z=None, clip=False, prediction="eps",
-              thresh=None):
+              thresh=None, known=None, keep=None):
     """One DDIM update (vd_ddim_step_pred): (x_prev, x0).  prediction="v": `eps` is the model's
     v output.  thresh=(p, threshold_max): dynamic thresholding (vd_x0_abs_quantile +
-    vd_ddim_step_thr) instead of the static clamp."""
+    vd_ddim_step_thr) instead of the static clamp.
+    known / keep: a masked step (vd_ddim_step_known, include/vdiff.h): `known` is a clip like xt
+    and `keep` an fp32 [Bk, S] mask over the spatial positions, Bk in (1, B), broadcast over the
+    channels; where keep is 1 the step's x0 is the known value and x_prev stays on the line from
+    xt to it whatever the model says, where it is 0 the step is unchanged, in between the two are
+    blended.  The same keywords on ddim_step_cfg, dpm_step and dpm_step_cfg."""
     rule_args = (z, t, t_prev, acp, eta, prediction_id(prediction))
     return _sampler_step("ddim_step", _DDIMArgs, rule_args, xt, eps, None, 1.0, 0.0, clip, thresh,
-                         None, None)
+                         None, None, known, keep)
 
 
 def ddim_step_cfg(xt, eps_c, eps_u, t, t_prev, acp, scale, rescale=0.0, eta=0.0, z=None,
-                  clip=False, out=None, dup=None, prediction="eps", thresh=None):
+                  clip=False, out=None, dup=None, prediction="eps", thresh=None, known=None,
+                  keep=None):
     """ddim_step on the guided noise of cfg_combine, in one pass (vd_ddim_step_cfg_pred):
     (x_prev, x0).  out: x_prev's buffer (may be xt itself); dup: a second buffer that receives
     the same x_prev values.  prediction="v": eps_c / eps_u are the model's two v outputs; the
@@ -411,26 +461,28 @@ def ddim_step_cfg(xt, eps_c, eps_u, t, t_prev, acp, scale, rescale=0.0, eta=0.0,
     x0 (vd_x0_abs_quantile + vd_ddim_step_thr) instead of the static clamp."""
     rule_args = (z, t, t_prev, acp, eta, prediction_id(prediction))
     return _sampler_step("ddim_step_cfg", _DDIMArgs, rule_args, xt, eps_c, eps_u, scale, rescale,
-                         clip, thresh, out, dup)
+                         clip, thresh, out, dup, known, keep)
 
 
-def dpm_step(xt, eps, x0_hist, coef, step, clip=False, out=None, thresh=None):
+def dpm_step(xt, eps, x0_hist, coef, step, clip=False, out=None, thresh=None, known=None,
+             keep=None):
     """One DPM-Solver++(2M) update (vd_dpm_step) from row `step` of the sampler's coefficient
     table: (x_prev, x0).  x0_hist holds the previous step's x0 and is overwritten in place with
     this step's (the returned x0 is that buffer); a row with C == 0 does not read it.  step: a
     device int64 scalar.  out: x_prev's buffer (may be xt itself).  thresh=(p, threshold_max):
     dynamic thresholding (vd_x0_abs_quantile + vd_dpm_step_thr) instead of the static clamp;
-    x_prev and the history get the thresholded x0."""
+    x_prev and the history get the thresholded x0.  known / keep: as in ddim_step
+    (vd_dpm_step_known); the history receives the known values where keep is 1."""
     return _sampler_step("dpm_step", _DPMArgs, (x0_hist, coef, step), xt, eps, None, 1.0, 0.0,
-                         clip, thresh, out, None)
+                         clip, thresh, out, None, known, keep)
 
 
 def dpm_step_cfg(xt, eps_c, eps_u, x0_hist, coef, step, scale, rescale=0.0, clip=False,
-                 out=None, dup=None, thresh=None):
+                 out=None, dup=None, thresh=None, known=None, keep=None):
     """dpm_step on the guided noise of cfg_combine, in one pass (vd_dpm_step_cfg): (x_prev, x0).
-    out / dup and thresh as in ddim_step_cfg."""
+    out / dup, thresh, known and keep as in ddim_step_cfg."""
     return _sampler_step("dpm_step", _DPMArgs, (x0_hist, coef, step), xt, eps_c, eps_u, scale,
-                         rescale, clip, thresh, out, dup)
+                         rescale, clip, thresh, out, dup, known, keep)
 
 
 def _window_args(name, long_, win, plan):

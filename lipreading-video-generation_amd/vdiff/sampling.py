@@ -20,7 +20,7 @@ import warnings
 import torch
 
 from . import hipgraph, ops
-from .schedulers import (DDIMSampler, DPMSolverSampler, WindowPlan, _sqrt_tables,
+from .schedulers import (DDIMSampler, DPMSolverSampler, WindowPlan, _mask_options, _sqrt_tables,
                          _thresh_kw)
 
 
@@ -144,20 +144,27 @@ class DDIMGraph:
     so the doubled input stays current without a copy; the doubled cond / audio / timestep
     buffers and the null audio are built here, before capture (no memset node in the step).
 
+    known / keep (masked sampling, _masked_start's pair): static operands of the captured step
+    kernel, which takes the masked entry point in the plain one's place -- the same node counts,
+    no copy per step.
+
     The subclasses change one thing each: DPMGraph the update rule (_rule_buffers, _update), the Long
     classes the denoiser."""
 
-    def __init__(self, model, sampler, cond, feats, xt, guidance_scale=1.0, guidance_rescale=0.0):
+    @_mask_options
+    def __init__(self, model, sampler, cond, feats, xt, guidance_scale=1.0, guidance_rescale=0.0,
+                 *, known=None, keep=None):
         guided = float(guidance_scale) != 1.0
         self._setup(_Direct(model, cond, feats, xt, guided), sampler, xt, guidance_scale,
-                    guidance_rescale)
+                    guidance_rescale, known, keep)
         if guided:
             self.x2 = self.saved
 
-    def _setup(self, denoise, sampler, xt, scale, rescale):
+    def _setup(self, denoise, sampler, xt, scale, rescale, known=None, keep=None):
         """The buffers of every step graph.  The timestep buffers have denoise.rows rows (B, 2B
         guided, or one per window of the batch); the step kernels read the first B."""
         self.denoise, self.sampler = denoise, sampler
+        self.mask = {} if known is None else dict(known=known, keep=keep)
         self.scale, self.rescale = float(scale), float(rescale)
         self.guided = denoise.guided
         self.graph = None
@@ -190,10 +197,12 @@ class DDIMGraph:
         if self.guided:
             _, x0 = ops.ddim_step_cfg(self.xt, *out, self.t[:B], self.tp[:B], self.acp,
                                       self.scale, self.rescale, clip=s.clip_x0, out=self.xt,
-                                      dup=self.dup, prediction=s.prediction, **_thresh_kw(s))
+                                      dup=self.dup, prediction=s.prediction, **_thresh_kw(s),
+                                      **self.mask)
             return x0
         xp, x0 = ops.ddim_step(self.xt, out, self.t[:B], self.tp[:B], self.acp, eta=0.0,
-                               clip=s.clip_x0, prediction=s.prediction, **_thresh_kw(s))
+                               clip=s.clip_x0, prediction=s.prediction, **_thresh_kw(s),
+                               **self.mask)
         self.xt.copy_(xp.view_as(self.xt))
         return x0
 
@@ -256,10 +265,11 @@ class DPMGraph(DDIMGraph):
         clip, thr = self.sampler.clip_x0, _thresh_kw(self.sampler)
         if self.guided:
             ops.dpm_step_cfg(self.xt, *out, self.x0, self.coef, self.idx, self.scale,
-                             self.rescale, clip=clip, out=self.xt, dup=self.dup, **thr)
+                             self.rescale, clip=clip, out=self.xt, dup=self.dup, **thr,
+                             **self.mask)
         else:
             ops.dpm_step(self.xt, out, self.x0, self.coef, self.idx, clip=clip, out=self.xt,
-                         **thr)
+                         **thr, **self.mask)
         return self.x0
 
 
@@ -269,23 +279,65 @@ class LongDDIMGraph(DDIMGraph):
     on the long tensors.  windows: the clip's WindowedDenoiser, which says whether the step is
     guided."""
 
-    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0):
+    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0,
+                 known=None, keep=None):
         self.windows = windows
-        self._setup(windows, sampler, xt, guidance_scale, guidance_rescale)
+        self._setup(windows, sampler, xt, guidance_scale, guidance_rescale, known, keep)
 
 
 class LongDPMGraph(DPMGraph):
     """DPMGraph for a long clip: gather + forward + blend, then vd_dpm_step (vd_cfg_stats +
     vd_dpm_step_cfg guided) in place on the long latent and its x0 history."""
 
-    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0):
+    def __init__(self, model, sampler, windows, xt, guidance_scale=1.0, guidance_rescale=0.0,
+                 known=None, keep=None):
         self.windows = windows
-        self._setup(windows, sampler, xt, guidance_scale, guidance_rescale)
+        self._setup(windows, sampler, xt, guidance_scale, guidance_rescale, known, keep)
+
+
+# ------------------------------------------------------------------ masked sampling
+def _masked_start(sampler, z, known, keep):
+    """Masked sampling's operands, checked once (host syncs are fine here: this runs before the
+    loop and before any capture): (the initial sample, known, keep) -- or (z, None, None)
+    without a mask.
+
+    known: the clip to keep, of the sample's shape [B, C, *spatial]; it is cast to the sample's
+    dtype and device.  keep: the mask, [Bk, 1, *spatial] (schedulers.keep_mask) or [Bk, S], Bk in
+    (1, B), values in [0, 1]; it becomes the step kernel's contiguous fp32 [Bk, S].  The sample
+    starts as z + k (q_sample(x_k, z, t0) - z) with z the driver's own noise and t0 the first
+    timestep: where k == 1 it is the known clip noised to t0 with that very z (exactly
+    q_sample's value), where k == 0 it is z."""
+    if known is None and keep is None:
+        return z, None, None
+    if known is None or keep is None:
+        raise ValueError("masked sampling: known and keep are given together or not at all")
+    B, spatial = z.shape[0], tuple(z.shape[2:])
+    if tuple(known.shape) != tuple(z.shape):
+        raise ValueError(f"masked sampling: known {tuple(known.shape)} for a sample of shape "
+                         f"{tuple(z.shape)}")
+    S = z[0, 0].numel()
+    if keep.dim() == 2:
+        ok = keep.shape[0] in (1, B) and keep.shape[1] == S
+    else:
+        ok = keep.shape[0] in (1, B) and tuple(keep.shape[1:]) == (1,) + spatial
+    if not ok:
+        raise ValueError(f"masked sampling: keep {tuple(keep.shape)} is neither [Bk, 1, "
+                         f"{', '.join(str(d) for d in spatial)}] nor [Bk, {S}], Bk in (1, {B})")
+    known = known.to(device=z.device, dtype=z.dtype).contiguous()
+    keep = keep.to(device=z.device, dtype=torch.float32).reshape(keep.shape[0], S).contiguous()
+    if not bool(((keep >= 0) & (keep <= 1)).all()):
+        raise ValueError("masked sampling: keep has values outside [0, 1]")
+    t0 = torch.full((B,), int(sampler.timesteps[0]), dtype=torch.int64, device=z.device)
+    acp = sampler.acp.to(z.device)
+    q = ops.q_sample(known, z.contiguous(), t0, acp.sqrt().contiguous(),
+                     (1 - acp).sqrt().contiguous())
+    k = keep.view((keep.shape[0], 1) + spatial).to(z.dtype)
+    return torch.where(k >= 1, q, z + k * (q - z)), known, keep
 
 
 # ------------------------------------------------------------------ the driver
 def _sample(model, sampler, dpm, cond, audio, shape, generator, callback, scale, rescale,
-            plan=None, window_batch=None):
+            plan=None, window_batch=None, known=None, keep=None):
     """sample_ddim / sample_dpm (dpm: the 2M update rule) and, with a plan, sample_long.  On a
     GPU one step is captured and replayed unless VDIFF_DDIM_GRAPH=0 or DDIM's eta != 0; the
     eager loop launches the same kernels on the same operands."""
@@ -293,6 +345,8 @@ def _sample(model, sampler, dpm, cond, audio, shape, generator, callback, scale,
     device = cond.device
     feats = _encode(model, audio)
     xt = torch.randn(shape, generator=generator, device=device)
+    xt, known, keep = _masked_start(sampler, xt, known, keep)
+    mask = {} if known is None else dict(known=known, keep=keep)  # a sampler need not know them
     guided = scale != 1.0
     windows = None
     if plan is not None:
@@ -300,10 +354,11 @@ def _sample(model, sampler, dpm, cond, audio, shape, generator, callback, scale,
     if (device.type == "cuda" and os.environ.get("VDIFF_DDIM_GRAPH", "1") != "0"
             and (dpm or sampler.eta == 0)):
         if windows is None:
-            g = (DPMGraph if dpm else DDIMGraph)(model, sampler, cond, feats, xt, scale, rescale)
+            g = (DPMGraph if dpm else DDIMGraph)(model, sampler, cond, feats, xt, scale, rescale,
+                                                 **mask)
         else:
             g = (LongDPMGraph if dpm else LongDDIMGraph)(model, sampler, windows, xt, scale,
-                                                         rescale)
+                                                         rescale, **mask)
         try:
             g.capture()
         except GraphUnsafe as e:
@@ -321,7 +376,7 @@ def _sample(model, sampler, dpm, cond, audio, shape, generator, callback, scale,
         t = torch.full((denoise.rows,), int(sampler.timesteps[i]), dtype=torch.int64,
                        device=device)
         out = denoise(xt, t)
-        kw = {"x0_last": x0} if dpm else {}
+        kw = dict(mask, x0_last=x0) if dpm else mask
         if guided:
             eps_c, eps_u = out.chunk(2)
             xt, x0 = sampler.step_guided(xt, eps_c, eps_u, i, scale, rescale, **kw)
@@ -332,9 +387,10 @@ def _sample(model, sampler, dpm, cond, audio, shape, generator, callback, scale,
     return xt, x0
 
 
+@_mask_options
 @torch.no_grad()
 def sample_ddim(model, sampler, cond, audio, shape, generator=None, callback=None,
-                guidance_scale=1.0, guidance_rescale=0.0):
+                guidance_scale=1.0, guidance_rescale=0.0, *, known=None, keep=None):
     """DDIM sampling (build extension of test.py:51-83): audio encoded once, packed conv
     weights reused across steps (ops.frozen_weights).
 
@@ -342,29 +398,41 @@ def sample_ddim(model, sampler, cond, audio, shape, generator=None, callback=Non
     2B -- rows [0, B) with the encoded audio, rows [B, 2B) with the null audio (zeros, what
     Trainer(audio_drop_prob=...) trains on) -- and steps on eps_u + w (eps_c - eps_u),
     std-rescaled per sample by guidance_rescale (Lin et al. 2023; 0 = off).  w == 1 is the
-    unguided path, unchanged."""
+    unguided path, unchanged.
+
+    known / keep: masked sampling (inpainting, continuation).  `known` is a clip of `shape`,
+    `keep` a mask over its frames and pixels (schedulers.keep_mask; _masked_start for the
+    accepted shapes): where keep is 1 the result is the known clip -- the returned x0 and sample
+    equal it there -- where it is 0 the model generates, conditioned on the kept part through
+    its own receptive field, and in between the step kernel blends the two x0.  The kept part is
+    replaced inside the step kernel at every step (ops.ddim_step), eager and replayed alike;
+    eta must be 0 for the kept part to stay exact.  The same keywords on sample_dpm and
+    sample_long."""
     with ops.frozen_weights():
         return _sample(model, sampler, False, cond, audio, shape, generator, callback,
-                       float(guidance_scale), float(guidance_rescale))
+                       float(guidance_scale), float(guidance_rescale), known=known, keep=keep)
 
 
+@_mask_options
 @torch.no_grad()
 def sample_dpm(model, sampler, cond, audio, shape, generator=None, callback=None,
-               guidance_scale=1.0, guidance_rescale=0.0):
+               guidance_scale=1.0, guidance_rescale=0.0, *, known=None, keep=None):
     """DPM-Solver++(2M) sampling (schedulers.DPMSolverSampler) with sample_ddim's contract:
     audio encoded once, packed conv weights reused across the steps, callback(i, xt, x0) at
     every step, classifier-free audio guidance as one forward at batch 2B, and on a GPU one
     replayed graph (DPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which launches the same
-    kernels on the same operands)."""
+    kernels on the same operands).  known / keep: masked sampling as in sample_ddim; the x0
+    history holds the known clip where keep is 1."""
     with ops.frozen_weights():
         return _sample(model, sampler, True, cond, audio, shape, generator, callback,
-                       float(guidance_scale), float(guidance_rescale))
+                       float(guidance_scale), float(guidance_rescale), known=known, keep=keep)
 
 
+@_mask_options
 @torch.no_grad()
 def sample_long(model, sampler, cond, audio, shape, window, stride=None, blend="triangle",
                 window_batch=None, generator=None, callback=None, guidance_scale=1.0,
-                guidance_rescale=0.0):
+                guidance_rescale=0.0, *, known=None, keep=None):
     """Sampling of a clip longer than the denoiser's window, with sample_ddim's contract:
     returns (x_T_end, x0) of `shape` = (B, 3, L, H, W); `sampler` a DDIMSampler or a
     DPMSolverSampler (TypeError otherwise); `audio` the L frames' windows or encoded features.
@@ -379,7 +447,12 @@ def sample_long(model, sampler, cond, audio, shape, window, stride=None, blend="
     the L frames and routed to the windows before the loop.  On a GPU one step is captured and
     replayed (LongDDIMGraph / LongDPMGraph; VDIFF_DDIM_GRAPH=0 selects the eager loop, which
     launches the same kernels on the same operands).  L == window is one window: sample_ddim /
-    sample_dpm run as they are."""
+    sample_dpm run as they are.
+
+    known / keep: masked sampling as in sample_ddim, on the long latent (the step kernel sees
+    it, not the windows): known is [B, 3, L, H, W]-shaped and keep covers the L frames.
+    Continuing a clip from its first K frames is keep = schedulers.keep_mask(L, H, W,
+    generate_box=(0, 1, 0, 1), keep_frames=K) with those frames filled into `known`."""
     if not isinstance(sampler, (DDIMSampler, DPMSolverSampler)):
         raise TypeError(f"sample_long: sampler must be a DDIMSampler or a DPMSolverSampler, "
                         f"got {type(sampler).__name__}")
@@ -392,10 +465,12 @@ def sample_long(model, sampler, cond, audio, shape, window, stride=None, blend="
     if plan.num_windows == 1:
         return (sample_dpm if dpm else sample_ddim)(
             model, sampler, cond, audio, shape, generator=generator, callback=callback,
-            guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
+            guidance_scale=guidance_scale, guidance_rescale=guidance_rescale, known=known,
+            keep=keep)
     with ops.frozen_weights():
         return _sample(model, sampler, dpm, cond, audio, shape, generator, callback,
-                       float(guidance_scale), float(guidance_rescale), plan, window_batch)
+                       float(guidance_scale), float(guidance_rescale), plan, window_batch,
+                       known, keep)
 
 
 # ------------------------------------------------------------------ ancestral DDPM

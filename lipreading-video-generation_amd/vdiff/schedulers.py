@@ -10,6 +10,7 @@ injected (tests) or is drawn with torch.randn_like on the tensor's device.
 from __future__ import annotations
 
 import functools
+import inspect
 import math
 
 import torch
@@ -141,6 +142,19 @@ class CosineNoiseScheduler(_Tables):
                                    self._dev("sqrt_one_minus_alphas_cumprod", d))
 
 
+def _mask_options(fn):
+    """Marks the keyword-only options known=None, keep=None of masked sampling on fn and keeps
+    them out of the signature that introspection reports: the positional parameter lists of the
+    samplers' steps, of the sampling functions and of the step graphs are what callers and the
+    earlier tests rely on and stay exactly what they were, as _prediction_keyword keeps the
+    initialisers'.  fn itself takes the two keywords; fn.__kwdefaults__ names them."""
+    sig = inspect.signature(fn)
+    assert all(sig.parameters[n].kind is inspect.Parameter.KEYWORD_ONLY for n in ("known", "keep"))
+    fn.__signature__ = sig.replace(parameters=[p for n, p in sig.parameters.items()
+                                               if n not in ("known", "keep")])
+    return fn
+
+
 class DDIMSampler:
     """DDIM (eta = 0: deterministic) over a subsequence of a DDPM schedule's acp table
     (build extension: the reference samples with 500-step DDPM V2, test.py:111).
@@ -183,16 +197,21 @@ class DDIMSampler:
         return tuple(torch.full((xt.shape[0],), int(ts[i]), dtype=torch.int64, device=xt.device)
                      for ts in (self.timesteps, self.prev_timesteps))
 
-    def step(self, xt, noise_pred, i, z=None):
-        """One update from self.timesteps[i] to self.prev_timesteps[i]: (x_prev, x0)."""
+    @_mask_options
+    def step(self, xt, noise_pred, i, z=None, *, known=None, keep=None):
+        """One update from self.timesteps[i] to self.prev_timesteps[i]: (x_prev, x0).  known /
+        keep: a masked step (ops.ddim_step; keep_mask builds the usual masks)."""
         t, tp = self._t_tp(xt, i)
         if self.eta > 0 and z is None:
             z = torch.randn_like(xt)
         return ops.ddim_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), t, tp,
                              self._acp(xt.device), eta=self.eta, z=z, clip=self.clip_x0,
-                             prediction=self.prediction, **_thresh_kw(self))
+                             prediction=self.prediction, known=known, keep=keep,
+                             **_thresh_kw(self))
 
-    def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, z=None):
+    @_mask_options
+    def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, z=None, *, known=None,
+                    keep=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
         by `rescale`: guide, rescale and update in one kernel (ops.ddim_step_cfg)."""
         t, tp = self._t_tp(xt, i)
@@ -201,7 +220,60 @@ class DDIMSampler:
         return ops.ddim_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
                                  eps_u.contiguous().to(xt.dtype), t, tp, self._acp(xt.device),
                                  scale, rescale, eta=self.eta, z=z, clip=self.clip_x0,
-                                 prediction=self.prediction, **_thresh_kw(self))
+                                 prediction=self.prediction, known=known, keep=keep,
+                                 **_thresh_kw(self))
+
+
+def keep_mask(T, H, W, *, generate_box=(0.5, 1.0, 0.0, 1.0), keep_frames=0, feather=0):
+    """The keep mask of masked sampling (the `keep` of the samplers and of sample_ddim /
+    sample_dpm / sample_long): fp32 [1, 1, T, H, W], 1 where the known clip is kept, 0 where the
+    model generates.
+
+    generate_box = (y0, y1, x0, x1), fractions of the height and the width: the rows round(y0 H)
+    .. round(y1 H) - 1 and the columns round(x0 W) .. round(x1 W) - 1 are generated, everything
+    outside is kept.  The default is the lower half of the frame (the mouth region of a centred
+    face).  keep_frames = K: the first K frames are kept whole, whatever the box says; continuing
+    a clip from K given frames is generate_box=(0, 1, 0, 1), keep_frames=K.  feather = F > 0: a
+    linear ramp just inside the box edges, keep = 1 - (d + 1) / (F + 1) for a pixel d = 0 .. F - 1
+    pixels inside the nearest edge of the box that borders kept pixels (an edge on the frame's
+    border has no ramp), so the blend of the step kernel fades from the known clip into the
+    generated region."""
+    T, H, W, K, F = int(T), int(H), int(W), int(keep_frames), int(feather)
+    if min(T, H, W) < 1:
+        raise ValueError(f"keep_mask: empty clip ({T}, {H}, {W})")
+    try:
+        y0, y1, x0, x1 = (float(v) for v in generate_box)
+    except (TypeError, ValueError):
+        raise ValueError(f"keep_mask: generate_box {generate_box!r}: four fractions y0, y1, x0, "
+                         "x1") from None
+    if not (0.0 <= y0 < y1 <= 1.0 and 0.0 <= x0 < x1 <= 1.0):
+        raise ValueError(f"keep_mask: generate_box {generate_box!r} needs 0 <= y0 < y1 <= 1 and "
+                         "0 <= x0 < x1 <= 1")
+    if not 0 <= K <= T:
+        raise ValueError(f"keep_mask: keep_frames {keep_frames} outside [0, {T}]")
+    if F < 0:
+        raise ValueError(f"keep_mask: feather {feather} < 0")
+    r0, r1, c0, c1 = round(y0 * H), round(y1 * H), round(x0 * W), round(x1 * W)
+    if r0 >= r1 or c0 >= c1:
+        raise ValueError(f"keep_mask: generate_box {generate_box!r} is empty at {H} x {W}")
+    big = float(H + W + F)  # an edge on the frame's border: no kept pixel beyond it, no ramp
+    rows = torch.arange(H, dtype=torch.float64).view(H, 1)
+    cols = torch.arange(W, dtype=torch.float64).view(1, W)
+    d = torch.full((H, W), big, dtype=torch.float64)
+    if r0 > 0:
+        d = torch.minimum(d, rows - r0)
+    if r1 < H:
+        d = torch.minimum(d, r1 - 1 - rows)
+    if c0 > 0:
+        d = torch.minimum(d, cols - c0)
+    if c1 < W:
+        d = torch.minimum(d, c1 - 1 - cols)
+    inside = (rows >= r0) & (rows < r1) & (cols >= c0) & (cols < c1)
+    ramp = (1.0 - (d + 1.0) / (F + 1.0)).clamp(0.0, 1.0) if F > 0 else torch.zeros_like(d)
+    frame = torch.where(inside, ramp, torch.ones_like(d))
+    m = frame.view(1, H, W).repeat(T, 1, 1)
+    m[:K] = 1.0
+    return m.float().view(1, 1, T, H, W)
 
 
 class WindowPlan:
@@ -408,18 +480,23 @@ class DPMSolverSampler:
         coef, idx = self._tables(xt.device)
         return x0_last, coef, idx[i:i + 1]
 
-    def step(self, xt, noise_pred, i, x0_last=None):
+    @_mask_options
+    def step(self, xt, noise_pred, i, x0_last=None, *, known=None, keep=None):
         """One update from self.timesteps[i] to self.prev_timesteps[i]: (x_prev, x0).  x0_last:
         the x0 that step i - 1 returned; it is overwritten in place with this step's x0 and
-        returned.  None is allowed where the row does not read it (C == 0)."""
+        returned.  None is allowed where the row does not read it (C == 0).  known / keep: a
+        masked step (ops.dpm_step)."""
         hist, coef, idx = self._row(xt, i, x0_last)
         return ops.dpm_step(xt.contiguous(), noise_pred.contiguous().to(xt.dtype), hist, coef,
-                            idx, clip=self.clip_x0, **_thresh_kw(self))
+                            idx, clip=self.clip_x0, known=known, keep=keep, **_thresh_kw(self))
 
-    def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, x0_last=None):
+    @_mask_options
+    def step_guided(self, xt, eps_c, eps_u, i, scale, rescale=0.0, x0_last=None, *, known=None,
+                    keep=None):
         """step() on the classifier-free guided noise eps_u + scale (eps_c - eps_u), std-rescaled
         by `rescale`: guide, rescale and update in one kernel (ops.dpm_step_cfg)."""
         hist, coef, idx = self._row(xt, i, x0_last)
         return ops.dpm_step_cfg(xt.contiguous(), eps_c.contiguous().to(xt.dtype),
                                 eps_u.contiguous().to(xt.dtype), hist, coef, idx, scale,
-                                rescale, clip=self.clip_x0, **_thresh_kw(self))
+                                rescale, clip=self.clip_x0, known=known, keep=keep,
+                                **_thresh_kw(self))

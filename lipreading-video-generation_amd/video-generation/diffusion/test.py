@@ -5,6 +5,8 @@
                    [--guidance-scale 1.0] [--guidance-rescale 0.0] [--prediction eps|v]
                    [--clip-frames L] [--window-stride S] [--window-blend triangle|uniform]
                    [--window-batch N]
+                   [--known clip.npy [--keep-mask mask.npy | --generate-box Y0 Y1 X0 X1
+                                      --keep-frames K --mask-feather PX]]
 
 Reference API kept (importable without running anything, unlike the reference script):
   * `config` -- the dict of test.py:33-49 (same keys; `ldm_params` may also carry the
@@ -37,6 +39,7 @@ import _vdiff_path  # noqa: F401
 from vdiff.engine import (reinit_nonzero, sample_ddim, sample_dpm, sample_long, synthetic_clip,
                           v_to_eps)
 from vdiff.ops import cfg_combine, frozen_weights
+from vdiff.schedulers import keep_mask
 
 from linear_noise_scheduler import LinearNoiseSchedulerV2
 from noise_scheduler import DDIMSampler, DPMSolverSampler
@@ -226,7 +229,40 @@ def parse(argv=None):
                          "(--sampler ddim|dpm++; for guidance scales well above 1)")
     ap.add_argument("--threshold-max", type=float, default=None, metavar="M",
                     help="upper bound of the dynamic threshold s (default: none)")
+    ap.add_argument("--known", default=None, metavar="FILE.npy",
+                    help="masked sampling (--sampler ddim|dpm++): a clip to keep, float in "
+                         "[-1, 1], shaped like the sample without its batch axis ([3, H, W], "
+                         "--dims 3: [3, frames, H, W]); the mask flags say where.  Default mask: "
+                         "the lower half of every frame is generated")
+    ap.add_argument("--keep-mask", default=None, metavar="FILE.npy",
+                    help="the mask itself, float in [0, 1] over the frames and pixels ([H, W], "
+                         "--dims 3: [frames, H, W]): 1 keeps --known, 0 generates, in between "
+                         "blends; excludes the three flags below")
+    ap.add_argument("--generate-box", type=float, nargs=4, default=None,
+                    metavar=("Y0", "Y1", "X0", "X1"),
+                    help="the generated region as fractions of the height and the width (default "
+                         "0.5 1 0 1: the lower half); everything outside is kept")
+    ap.add_argument("--keep-frames", type=int, default=None, metavar="K",
+                    help="keep the first K frames whole (continue a clip: with --generate-box 0 1 "
+                         "0 1)")
+    ap.add_argument("--mask-feather", type=int, default=None, metavar="PX",
+                    help="linear ramp of PX pixels just inside the box edges")
     args = ap.parse_args(argv)
+    box_flags = [f for f, v in (("--generate-box", args.generate_box),
+                                ("--keep-frames", args.keep_frames),
+                                ("--mask-feather", args.mask_feather)) if v is not None]
+    mask_flags = box_flags + (["--keep-mask"] if args.keep_mask is not None else [])
+    if args.known is None and mask_flags:
+        ap.error(f"{', '.join(mask_flags)}: masked sampling needs --known")
+    if args.known is not None and args.sampler not in ("ddim", "dpm++"):
+        ap.error(f"--known needs --sampler ddim or dpm++ (got {args.sampler}: the known clip is "
+                 "kept inside their step kernel)")
+    if args.keep_mask is not None and box_flags:
+        ap.error(f"--keep-mask excludes {', '.join(box_flags)}")
+    if args.keep_frames is not None and args.keep_frames < 0:
+        ap.error("--keep-frames must be at least 0")
+    if args.mask_feather is not None and args.mask_feather < 0:
+        ap.error("--mask-feather must be at least 0")
     if args.dynamic_threshold is not None:
         if args.sampler not in ("ddim", "dpm++"):
             ap.error(f"--dynamic-threshold needs --sampler ddim or dpm++ (got {args.sampler}: "
@@ -258,6 +294,36 @@ def _check_long(args, clip_frames):
                          f"window (--frames {args.frames}); windowed sampling needs --dims 3 and "
                          f"--sampler ddim or dpm++ (got --dims {args.dims}, --sampler "
                          f"{args.sampler})")
+
+
+def _load_mask(args, shape):
+    """The `known` / `keep` keywords of masked sampling from --known and the mask flags ({}
+    without --known).  shape: the sample's, (1, 3, [frames,] H, W)."""
+    if args.known is None:
+        return {}
+    known = np.load(args.known, allow_pickle=False)
+    if tuple(known.shape) != tuple(shape[1:]) or not np.issubdtype(known.dtype, np.floating):
+        raise SystemExit(f"test.py: --known holds {known.dtype} {tuple(known.shape)}; the sample "
+                         f"is float {tuple(shape[1:])}")
+    if not (np.isfinite(known).all() and np.abs(known).max() <= 1.0):
+        raise SystemExit("test.py: --known has values outside [-1, 1]")
+    spatial = tuple(shape[2:])
+    if args.keep_mask is not None:
+        keep = np.load(args.keep_mask, allow_pickle=False)
+        if tuple(keep.shape) != spatial or not np.issubdtype(keep.dtype, np.floating):
+            raise SystemExit(f"test.py: --keep-mask holds {keep.dtype} {tuple(keep.shape)}; the "
+                             f"sample's frames and pixels are float {spatial}")
+        keep = torch.from_numpy(keep).float().view((1, 1) + spatial)
+    else:
+        frames = spatial[0] if len(spatial) == 3 else 1
+        try:
+            keep = keep_mask(frames, *spatial[-2:],
+                             generate_box=args.generate_box or (0.5, 1.0, 0.0, 1.0),
+                             keep_frames=args.keep_frames or 0, feather=args.mask_feather or 0)
+        except ValueError as e:
+            raise SystemExit(f"test.py: {e}") from None
+        keep = keep.view((1, 1) + spatial)
+    return dict(known=torch.from_numpy(known).float()[None], keep=keep)
 
 
 def main(argv=None):
@@ -322,12 +388,13 @@ def main(argv=None):
                                 stride=args.window_stride, blend=args.window_blend,
                                 window_batch=args.window_batch, generator=g, callback=cb,
                                 guidance_scale=args.guidance_scale,
-                                guidance_rescale=args.guidance_rescale)
+                                guidance_rescale=args.guidance_rescale,
+                                **_load_mask(args, shape))
             print("All images have been processed and saved.")
             return x0
         _, x0 = sample(model, sampler, cond, audio, shape, generator=g, callback=cb,
                        guidance_scale=args.guidance_scale,
-                       guidance_rescale=args.guidance_rescale)
+                       guidance_rescale=args.guidance_rescale, **_load_mask(args, shape))
         print("All images have been processed and saved.")
         return x0
     return sample_images(model, scheduler, cond, audio, n_timesteps=args.steps or 500,
