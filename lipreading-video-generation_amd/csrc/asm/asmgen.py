@@ -276,6 +276,32 @@ def frag_offsets(d, lane, nrow, ntr):
     return out
 
 
+def m16_chunk(ks, g):
+    """attention.hip m16_chunk: the 16-B chunk of a row that contraction slot group (ks, g) of a
+    v_mfma_f32_16x16x32_bf16 operand over head_dim holds (g = lane >> 4)."""
+    return 4 * ks + g
+
+
+def m16_row(it, i):
+    """attention.hip m16_row: the row (of a 32-row block) that MFMA row i of row tile `it` of a
+    16x16x32 A operand reads; accumulator rows 4 g .. 4 g + 3 are rows m16_row(it, 4 g) .. + 3."""
+    return 16 * (i >> 3) + 4 * ((i >> 2) & 1) + 8 * it + (i & 3)
+
+
+def frag_offsets16(d, lane):
+    """A lane's table entries for the 16x16x32 reads of a bf16 tile with d-element rows: the 4
+    row-fragment offsets (attention.hip mma_rows_nb<M16>: 2 it + ks, block row 0), then the 8
+    transposed-fragment offsets (mma_tr_nb<M16>: 2 dt + hi, 16-column tile dt of the tile's 64
+    columns, low / high half of the contraction group; sum0 = 0)."""
+    i, g = lane & 15, lane >> 4
+    out = [toff_bytes(d, m16_row(it, i), 8 * m16_chunk(ks, g))
+           for it in range(2) for ks in range(2)]
+    q4, p4 = i >> 2, i & 3
+    out += [toff_bytes(d, m16_row(hi, 4 * g) + q4, 16 * dt + 4 * p4)
+            for dt in range(4) for hi in range(2)]
+    return out
+
+
 def lds(V, name, k, off):
     """(base register, immediate) of LDS byte offset `off` from per-lane table entry k of
     `name` ('rowoff' / 'troff'; their +64 KiB copies are 'rowhi' / 'trhi')."""

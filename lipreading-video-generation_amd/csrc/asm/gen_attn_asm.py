@@ -25,14 +25,22 @@ buffer_load ... lds (tile t + 2 issued after the barrier of tile t), one s_barri
 tile behind s_waitcnt vmcnt(4).  The loop is unrolled by the 4 stages, so every LDS
 address is a per-lane constant (a table in .rodata, computed here with the formulas of
 attention.hip's toff / mma_rows / mma_tr / dma_tile) plus an immediate.
+
+MFMA shape, one per kernel, chosen by wall time at N = 262144 (DESIGN.md 4.1,
+profiles/r07_bwd_m16.md): vd_attn_bwd_dq_d64 runs on v_mfma_f32_32x32x16_bf16 as described
+above; vd_attn_bwd_dkdv_d64 (second half of this file) on v_mfma_f32_16x16x32_bf16, 128 MFMAs
+per 64-query tile, which holds a higher clock under the power limit.  Each kernel's HIP twin in
+attention.hip (attn_bwd_dq_pipe_kernel / attn_bwd_dkdv_pipe_kernel, bf16, D = 64) uses the
+same shape, fragment maps and MFMA sequence per accumulator, and the two must agree bit for
+bit (tests/test_gpu_attention_asm.py).
 """
 from __future__ import annotations
 
 import sys
 
 from asmgen import (Regs, Stream, add64, code_object_text, dma_at_gap, dma_issue, frag_offsets,
-                    kernel_text, lane_table_data, loop_tail, mad64, rsrc, scale_bf16, swz,
-                    wave_and_table)
+                    frag_offsets16, kernel_text, lane_table_data, loop_tail, m16_chunk, m16_row,
+                    mad64, rsrc, scale_bf16, swz, wave_and_table)
 from gen_d128 import gen_dkdv128, gen_dq128
 from gen_d256 import gen_dq256
 from gen_d256dk import gen_dkdv256
@@ -395,18 +403,27 @@ def gen_dq():
 # vd_attn_bwd_dkdv_d64: the arithmetic of attn_bwd_dkdv_pipe_kernel<bf16, 64> (S' = Q K'^T -
 # lse', dP = dO V^T - delta with the query on the accumulator rows and the key on the lane,
 # dV^T += dO^T P, dK^T += Q^T dS, K' = K * scale * log2 e) at one wave per SIMD: 4 waves x
-# 64 keys (2 key blocks kj) per workgroup.  Per 64-query tile (2 query blocks qb) a wave runs
-# 64 MFMAs and 192 VALU instructions.  MFMA order of iteration t:
-#   S/dP(t, qb0) [16] | dQ-less G(t-1, qb1) [16] | S/dP(t, qb1) [16] | barrier | G(t, qb0) [16]
+# 64 keys (2 key blocks kj) per workgroup, on v_mfma_f32_16x16x32_bf16 (attention.hip
+# kDkdvM16; the fragment maps are its m16_chunk / m16_row).  A 32 x 32 block is four 16 x 16
+# accumulator tiles (it = query rows, jt = keys): registers 4 (2 jt + it) .. + 3 of the block's
+# 16, so registers 8 jt .. + 7, packed, are the K = 32 B operand of the G products of key
+# tile jt.  Per 64-query tile (2 query blocks qb) a wave runs 128 MFMAs and 192 VALU
+# instructions.  MFMA order of iteration t:
+#   S/dP(t, qb0) [32] | G(t-1, qb1) [32] | S/dP(t, qb1) [32] | barrier | G(t, qb0) [32]
 # The barrier that publishes tile t+1 sits before the last group, so the fragment reads of
-# (t+1, qb0) -- rows of Q and dO, the row constants -- are issued under G(t, qb0).  The VALU
-# stream runs at 3 instructions per gap: the softmax of (t, qb0) in gaps 17..48, of (t, qb1)
-# in gaps 49..16 of the next iteration, each finishing just before its G group.
+# (t+1, qb0) -- rows of Q and dO, the row constants -- are issued under G(t, qb0).  A 16-cycle
+# gap hides 8 cycles of vector issue, so the VALU stream is cut into groups of about that
+# (one v_exp_f32, or two v_mul_f32, or two v_cvt_pk_bf16_f32), one group per gap: the softmax
+# of (t, qb0) in gaps 34..97, of (t, qb1) in gaps 98..33 of the next iteration, each finishing
+# just before its G group; one LDS read per gap.
 DK_STAGE = 16384          # Q tile | dO tile
 DK_RC = 768               # per stage: lse' (256 B) | delta (256 B) | junk (256 B)
 DK_RC_BYTES = 4 * DK_RC   # the row-constant region at LDS offset 0
 DK_KARG = 144
-DK_START = 17
+DK_START = 34
+DK_NM = 128               # MFMAs per tile
+DK_DMA_GAPS = (98, 102, 106, 110, 114)   # the 5 LDS-DMA pieces of tile t+3, after the barrier
+MFMA16 = "v_mfma_f32_16x16x32_bf16"
 RQ2, RK2, RV2, RO2, RL2, RD2, RDK2, RDV2 = ("s[60:63]", "s[64:67]", "s[68:71]", "s[72:75]",
                                             "s[76:79]", "s[80:83]", "s[84:87]", "s[88:91]")
 S2_WAVE, S2_K0, S2_M0, S2_ITER, S2_RCM0 = "s92", "s93", "s94", "s95", "s98"
@@ -415,37 +432,52 @@ RRC2 = "s[56:59]"  # this wave's row-constant DMA source (lse', delta, or lse' i
 
 def regs_dkdv():
     V, A = Regs("v"), Regs("a")
-    for name, n in (("tid", 1), ("lane", 1), ("rowoff", 4), ("troff", 4), ("dmaq", 2),
-                    ("dmao", 2), ("dmac", 2), ("rcv", 1), ("rcoff", 1), ("tmp", 4),
-                    ("stk", 2), ("tmp2", 2)):
+    for name, n in (("tid", 1), ("lane", 1), ("rowoff", 4), ("troff", 8), ("dmaq", 2),
+                    ("dmao", 2), ("dmac", 2), ("rcoff", 2), ("tmp", 4), ("stk", 2),
+                    ("tmp2", 2), ("rcv", 1)):
         V.alloc(name, n)
-    V.alloc("s", 64, 16)     # S' blocks [qb][kj]
+    V.alloc("s", 64, 16)     # S' blocks [qb][kj], tile (it, jt) at 4 (2 jt + it)
     V.alloc("dp", 64)        # dP blocks [qb][kj]
-    V.alloc("pp", 32)        # P as bf16 B operands [qb][kj] x 8
+    V.alloc("pp", 32)        # P as bf16 B operands [qb][kj][jt] x 4
     V.alloc("ds", 32)        # dS as bf16 B operands
-    V.alloc("il", 16)        # -lse' of the current query block's rows (srcC of S)
-    V.alloc("id", 16)        # -delta of those rows (srcC of dP)
-    A.alloc("kf", 32)        # K' fragments [kj][s]
-    A.alloc("vf", 32)        # V fragments [kj][s]
-    A.alloc("adk", 64)       # dK^T accumulators [i][kj]
-    A.alloc("adv", 64)       # dV^T accumulators [i][kj]
-    A.alloc("qrow", 16)      # Q row fragments of the current query block [s]
-    A.alloc("orow", 16)      # dO row fragments [s]
-    A.alloc("otr", 16)       # dO^T fragments of the G block [i][s2]
-    A.alloc("qtr", 16)       # Q^T fragments [i][s2]
+    V.alloc("il", 8)         # -lse' of the current query block's rows [it] x 4 (srcC of S)
+    V.alloc("id", 8)         # -delta of those rows (srcC of dP)
+    A.alloc("kf", 32)        # K' fragments [kj][jt][ks]
+    A.alloc("vf", 32)        # V fragments [kj][jt][ks]
+    A.alloc("adk", 64)       # dK^T accumulators, tile (dt, kj, jt) at acc_idx
+    A.alloc("adv", 64)       # dV^T accumulators
+    A.alloc("qrow", 16)      # Q row fragments of the current query block [it][ks]
+    A.alloc("orow", 16)      # dO row fragments [it][ks]
+    A.alloc("otr", 16)       # dO^T fragments of the G block [dt] (lo 2 + hi 2)
+    A.alloc("qtr", 16)       # Q^T fragments [dt]
     return V, A
 
 
 def dk_lane_table():
+    """tab[wave][lane][32] u32: 0-3 row-fragment offsets (2 it + ks), 4-11 transposed-fragment
+    offsets (2 dt + hi) (asmgen.frag_offsets16), 12-13 DMA row in the tile and 14-15 its source
+    chunk * 16 (pieces i = 0, 1 of dma_tile<64, 4>), 16-17 the row-constant read bases (4 B x
+    the first accumulator row of the lane in row tile it = 0, 1), 18 the byte offset of the
+    lane's k-step-0 chunk in a global row, 19 its d offset in an output row."""
     base = lane_table()
+    out = []
     for w in range(NW):
         for lane in range(64):
-            base[w * 64 + lane][12] = 16 * (lane >> 5)  # row-constant read base (16 hh)
-    return base
+            g = lane >> 4
+            out.append(frag_offsets16(64, lane) + base[w * 64 + lane][8:12]
+                       + [4 * m16_row(0, 4 * g), 4 * m16_row(1, 4 * g), 16 * m16_chunk(0, g), 8 * g]
+                       + [0] * 12)
+    return out
 
 
 def blk(qb, kj):
     return 2 * qb + kj
+
+
+def acc_idx(dt, kj, jt):
+    """Register offset in adk / adv of the 16 x 16 tile (d tile dt, key block kj, key tile jt):
+    the 32 x 32 block [dt >> 1][kj] as in the HIP kernel, tile (dt & 1, jt) inside it."""
+    return 16 * (2 * (dt >> 1) + kj) + 4 * (2 * jt + (dt & 1))
 
 
 def prologue_dkdv(st: Stream, V, A):
@@ -489,33 +521,38 @@ def prologue_dkdv(st: Stream, V, A):
     r(f"s_add_u32 {S2_M0}, {S2_M0}, {DK_RC_BYTES}")
     r(f"s_mov_b32 {S2_ITER}, s50")
     t0, t1 = V.r("tmp", 0), V.r("tmp", 1)
-    e(f"v_lshlrev_b32 {t0}, 6, {V.r('tid')}")
+    chunk, stoff = V.r("s", 62), V.r("s", 63)
+    e(f"v_lshlrev_b32 {t0}, 7, {V.r('tid')}")
     r(f"global_load_dwordx4 {V.r('rowoff', 0, 4)}, {t0}, s[96:97]")
     r(f"global_load_dwordx4 {V.r('troff', 0, 4)}, {t0}, s[96:97] offset:16")
-    r(f"global_load_dwordx2 {V.r('dmaq', 0, 2)}, {t0}, s[96:97] offset:32")
-    r(f"global_load_dwordx2 {V.r('dmac', 0, 2)}, {t0}, s[96:97] offset:40")
-    r(f"global_load_dword {V.r('rcoff')}, {t0}, s[96:97] offset:48")
-    # key rows of the wave: krow_kj = k0 + 32 kj + (lane & 31)
-    krow = [V.r("s", 60), V.r("s", 61)]
-    hh16 = V.r("s", 62)
-    e(f"v_and_b32 {krow[0]}, 31, {V.r('lane')}")
-    e(f"v_add_u32 {krow[0]}, {S2_K0}, {krow[0]}")
-    e(f"v_add_u32 {krow[1]}, 32, {krow[0]}")
-    e(f"v_lshrrev_b32 {hh16}, 5, {V.r('lane')}")
-    e(f"v_lshlrev_b32 {hh16}, 4, {hh16}")
+    r(f"global_load_dwordx4 {V.r('troff', 4, 4)}, {t0}, s[96:97] offset:32")
+    r(f"global_load_dwordx2 {V.r('dmaq', 0, 2)}, {t0}, s[96:97] offset:48")
+    r(f"global_load_dwordx2 {V.r('dmac', 0, 2)}, {t0}, s[96:97] offset:56")
+    r(f"global_load_dwordx2 {V.r('rcoff', 0, 2)}, {t0}, s[96:97] offset:64")
+    r(f"global_load_dwordx2 {V.r('s', 62, 2)}, {t0}, s[96:97] offset:72")
+    # key rows of the wave: krow[kj][jt] = k0 + 32 kj + 16 jt + (lane & 15)
+    krow = [[V.r("s", 56), V.r("s", 57)], [V.r("s", 58), V.r("s", 59)]]
+    e(f"v_and_b32 {krow[0][0]}, 15, {V.r('lane')}")
+    e(f"v_add_u32 {krow[0][0]}, {S2_K0}, {krow[0][0]}")
+    e(f"v_add_u32 {krow[0][1]}, 16, {krow[0][0]}")
+    e(f"v_add_u32 {krow[1][0]}, 32, {krow[0][0]}")
+    e(f"v_add_u32 {krow[1][1]}, 48, {krow[0][0]}")
+    r("s_waitcnt vmcnt(0)")
     kv = V["s"]  # K fragments staged in v[s .. s+31] for scaling
     for kj in range(2):
-        vk = V.r("dp", 60 + kj)
-        e(f"v_mul_lo_u32 {vk}, {krow[kj]}, s33")
-        e(f"v_add_u32 {vk}, {vk}, {hh16}")
-        for s in range(4):
-            r(f"buffer_load_dwordx4 v[{kv + 16 * kj + 4 * s}:{kv + 16 * kj + 4 * s + 3}], {vk}, "
-              f"{RK2}, 0 offen offset:{32 * s}")
-            r(f"buffer_load_dwordx4 {A.r('vf', 16 * kj + 4 * s, 4)}, {vk}, {RV2}, 0 offen "
-              f"offset:{32 * s}")
-        e(f"v_lshrrev_b32 {V.r('dp', 54)}, 1, {hh16}")
-        e(f"v_mul_lo_u32 {V.r('stk', kj)}, {krow[kj]}, s33")
-        e(f"v_add_u32 {V.r('stk', kj)}, {V.r('stk', kj)}, {V.r('dp', 54)}")
+        for jt in range(2):
+            vk = V.r("dp", 56 + 2 * kj + jt)
+            e(f"v_mul_lo_u32 {vk}, {krow[kj][jt]}, s33")
+            e(f"v_add_u32 {vk}, {vk}, {chunk}")
+            for ks in range(2):
+                w = 16 * kj + 4 * (2 * jt + ks)
+                r(f"buffer_load_dwordx4 v[{kv + w}:{kv + w + 3}], {vk}, {RK2}, 0 offen "
+                  f"offset:{64 * ks}")
+                r(f"buffer_load_dwordx4 {A.r('vf', w, 4)}, {vk}, {RV2}, 0 offen "
+                  f"offset:{64 * ks}")
+        # dK / dV store offsets of key tile jt = 0: krow * ts_bytes + 8 (lane >> 4)
+        e(f"v_mul_lo_u32 {V.r('stk', kj)}, {krow[kj][0]}, s33")
+        e(f"v_add_u32 {V.r('stk', kj)}, {V.r('stk', kj)}, {stoff}")
     r("s_waitcnt vmcnt(0)")
     scale_bf16(st, kv, 32, "s45", t0, t1, lambda w: A.r("kf", w))
     # DMA source offsets: Q / dO pieces row * stride + chunk * 16 ; row constants 4 lane
@@ -546,8 +583,6 @@ def prologue_dkdv(st: Stream, V, A):
     e(f"ds_write_b32 {V.r('tmp2', 1)}, {V.r('tmp', 0)} offset:{3 * DK_RC}")
     st.label(".Ldk_nozero")
     r("s_waitcnt lgkmcnt(0)")
-    for k in range(4):  # the loop's +32 KiB copies of the K^T / Q^T fragment offsets
-        e(f"v_add_u32 {V.r('tmp', k)}, 0x8000, {V.r('troff', k)}")
     for t in range(3):
         dma_issue(st, *dk_dma(V, t))
     r("s_waitcnt vmcnt(10)")
@@ -576,39 +611,41 @@ def dk_dma(V, stage):
 
 
 def dk_row_reads(V, A, stage, qb):
-    """Fragment reads of query block qb of the tile in `stage`: Q rows, dO rows, -lse' and
-    -delta of the block's rows (register 4g + e = row 8 g + 4 hh + e)."""
+    """Fragment reads of query block qb of the tile in `stage`: Q rows, dO rows [it][ks], -lse'
+    and -delta of the block's rows (register 4 it + e = row m16_row(it, 4 g) + e)."""
     out = []
     tq = DK_RC_BYTES + stage * DK_STAGE + qb * 4096
-    for s in range(4):
-        out.append((f"ds_read_b128 {A.r('qrow', 4 * s, 4)}, {V.r('rowoff', s)} offset:{tq}",
-                    ("Q", s)))
-        out.append((f"ds_read_b128 {A.r('orow', 4 * s, 4)}, {V.r('rowoff', s)} "
-                    f"offset:{tq + 8192}", ("O", s)))
-    for g in range(4):
-        rc = stage * DK_RC + qb * 128 + 32 * g
-        out.append((f"ds_read_b128 {V.r('il', 4 * g, 4)}, {V.r('rcoff')} offset:{rc}", ("L", g)))
-        out.append((f"ds_read_b128 {V.r('id', 4 * g, 4)}, {V.r('rcoff')} offset:{rc + 256}",
-                    ("D", g)))
+    for it in range(2):
+        for ks in range(2):
+            f = 2 * it + ks
+            out.append((f"ds_read_b128 {A.r('qrow', 4 * f, 4)}, {V.r('rowoff', f)} offset:{tq}",
+                        ("Q", it, ks)))
+            out.append((f"ds_read_b128 {A.r('orow', 4 * f, 4)}, {V.r('rowoff', f)} "
+                        f"offset:{tq + 8192}", ("O", it, ks)))
+    for it in range(2):
+        rc = stage * DK_RC + qb * 128
+        out.append((f"ds_read_b128 {V.r('il', 4 * it, 4)}, {V.r('rcoff', it)} offset:{rc}",
+                    ("L", it)))
+        out.append((f"ds_read_b128 {V.r('id', 4 * it, 4)}, {V.r('rcoff', it)} offset:{rc + 256}",
+                    ("D", it)))
     return out
 
 
 def dk_tr_reads(V, A, stage, qb):
     out = []
     tq = DK_RC_BYTES + stage * DK_STAGE + qb * 4096
-    for i in range(2):
-        for s2 in range(2):
-            for hi in range(2):
-                for x, name in ((8192, "otr"), (0, "qtr")):
-                    off, base = tq + x + s2 * 2048, V.r("troff", 2 * i + hi)
-                    if off > 65535:  # past the 16-bit immediate: the +32 KiB base copy
-                        off, base = off - 32768, V.r("tmp", 2 * i + hi)
-                    out.append((f"ds_read_b64_tr_b16 {A.r(name, 8 * i + 4 * s2 + 2 * hi, 2)}, "
-                                f"{base} offset:{off}", (name, i, s2, hi)))
+    for dt in range(4):
+        for hi in range(2):
+            for x, name in ((8192, "otr"), (0, "qtr")):
+                off = tq + x
+                assert off <= 65535  # the 16-bit immediate
+                out.append((f"ds_read_b64_tr_b16 {A.r(name, 4 * dt + 2 * hi, 2)}, "
+                            f"{V.r('troff', 2 * dt + hi)} offset:{off}", (name, dt, hi)))
     return out
 
 
 def dk_valu(V):
+    """The tile's 192 VALU instructions in gap-sized groups, 4 per register pair."""
     out = []
     for qb in range(2):
         for kj in range(2):
@@ -617,48 +654,44 @@ def dk_valu(V):
             P, G = V["pp"] + 8 * b, V["ds"] + 8 * b
             for k in range(8):
                 a, c = 2 * k, 2 * k + 1
-                out += [f"v_exp_f32 v{S + a}, v{S + a}", f"v_exp_f32 v{S + c}, v{S + c}",
-                        f"v_mul_f32 v{D + a}, v{D + a}, v{S + a}",
-                        f"v_mul_f32 v{D + c}, v{D + c}, v{S + c}",
-                        f"v_cvt_pk_bf16_f32 v{P + k}, v{S + a}, v{S + c}",
-                        f"v_cvt_pk_bf16_f32 v{G + k}, v{D + a}, v{D + c}"]
+                out += [[f"v_exp_f32 v{S + a}, v{S + a}"], [f"v_exp_f32 v{S + c}, v{S + c}"],
+                        [f"v_mul_f32 v{D + a}, v{D + a}, v{S + a}",
+                         f"v_mul_f32 v{D + c}, v{D + c}, v{S + c}"],
+                        [f"v_cvt_pk_bf16_f32 v{P + k}, v{S + a}, v{S + c}",
+                         f"v_cvt_pk_bf16_f32 v{G + k}, v{D + a}, v{D + c}"]]
     return out
 
 
 def dk_sdp(V, A, qb):
     out = []
-    for s in range(4):
+    for ks in range(2):
         for kj in range(2):
-            b = blk(qb, kj)
-            sv, dv = V.r("s", 16 * b, 16), V.r("dp", 16 * b, 16)
-            cs = V.r("il", 0, 16) if s == 0 else sv
-            cd = V.r("id", 0, 16) if s == 0 else dv
-            out.append((f"{MFMA} {sv}, {A.r('qrow', 4 * s, 4)}, {A.r('kf', 16 * kj + 4 * s, 4)}, "
-                        f"{cs}", (("Q", s),) + ((("L", 0), ("L", 1), ("L", 2), ("L", 3))
-                                                  if s == 0 else ())))
-            out.append((f"{MFMA} {dv}, {A.r('orow', 4 * s, 4)}, {A.r('vf', 16 * kj + 4 * s, 4)}, "
-                        f"{cd}", (("O", s),) + ((("D", 0), ("D", 1), ("D", 2), ("D", 3))
-                                                  if s == 0 else ())))
+            for it in range(2):
+                for jt in range(2):
+                    t = 16 * blk(qb, kj) + 4 * (2 * jt + it)
+                    sv, dv = V.r("s", t, 4), V.r("dp", t, 4)
+                    cs = V.r("il", 4 * it, 4) if ks == 0 else sv
+                    cd = V.r("id", 4 * it, 4) if ks == 0 else dv
+                    kf = 16 * kj + 4 * (2 * jt + ks)
+                    out.append((f"{MFMA16} {sv}, {A.r('qrow', 4 * (2 * it + ks), 4)}, "
+                                f"{A.r('kf', kf, 4)}, {cs}",
+                                (("Q", it, ks),) + ((("L", it),) if ks == 0 else ())))
+                    out.append((f"{MFMA16} {dv}, {A.r('orow', 4 * (2 * it + ks), 4)}, "
+                                f"{A.r('vf', kf, 4)}, {cd}",
+                                (("O", it, ks),) + ((("D", it),) if ks == 0 else ())))
     return out
 
 
 def dk_g(V, A, qb):
     out = []
-    for i in range(2):
-        for s2 in range(2):
+    for dt in range(4):
+        for acc_name, tr, x in (("adv", "otr", "pp"), ("adk", "qtr", "ds")):
             for kj in range(2):
-                b = blk(qb, kj)
-                acc = A.r("adv", 16 * (2 * i + kj), 16)
-                out.append((f"{MFMA} {acc}, {A.r('otr', 8 * i + 4 * s2, 4)}, "
-                            f"{V.r('pp', 8 * b + 4 * s2, 4)}, {acc}",
-                            tuple(("otr", i, s2, h) for h in range(2))))
-        for s2 in range(2):
-            for kj in range(2):
-                b = blk(qb, kj)
-                acc = A.r("adk", 16 * (2 * i + kj), 16)
-                out.append((f"{MFMA} {acc}, {A.r('qtr', 8 * i + 4 * s2, 4)}, "
-                            f"{V.r('ds', 8 * b + 4 * s2, 4)}, {acc}",
-                            tuple(("qtr", i, s2, h) for h in range(2))))
+                for jt in range(2):
+                    acc = A.r(acc_name, acc_idx(dt, kj, jt), 4)
+                    out.append((f"{MFMA16} {acc}, {A.r(tr, 4 * dt, 4)}, "
+                                f"{V.r(x, 8 * blk(qb, kj) + 4 * jt, 4)}, {acc}",
+                                tuple((tr, dt, h) for h in range(2))))
     return out
 
 
@@ -669,26 +702,28 @@ def emit_dk_iter(st: Stream, V, A, stage, valu):
     st.comment(f"---- query tile, ring stage {stage}")
     mf = dk_sdp(V, A, 0) + dk_g(V, A, 1) + dk_sdp(V, A, 1) + dk_g(V, A, 0)
     nm = len(mf)
+    assert nm == DK_NM == len(valu)
     slots = {}
-    for i, text in enumerate(valu):
-        slots.setdefault((DK_START + (i * nm) // len(valu)) % nm, []).append((text, None))
+    for i, grp in enumerate(valu):
+        slots[(DK_START + i) % nm] = [(text, None) for text in grp]
 
-    def put(slot0, lst, per=2):
+    def put(slot0, lst):
         for k, (text, rid) in enumerate(lst):
-            slots.setdefault(slot0 + k // per, []).insert(0, (text, rid))
+            slots[slot0 + k].insert(0, (text, rid))
 
-    put(2, dk_tr_reads(V, A, prev, 1))          # G(t-1, qb1) operands, tile t-1
-    put(18, dk_row_reads(V, A, stage, 1))       # (t, qb1) fragments
-    put(34, dk_tr_reads(V, A, stage, 0))        # G(t, qb0) operands
+    put(4, dk_tr_reads(V, A, prev, 1))          # G(t-1, qb1) operands, tile t-1
+    put(36, dk_row_reads(V, A, stage, 1))       # (t, qb1) fragments
+    put(68, dk_tr_reads(V, A, stage, 0))        # G(t, qb0) operands
     ops, adv = dk_dma(V, (stage + 3) % 4)
     for g in range(nm):
-        if g == 48:
+        if g == 96:
             st.raw("s_waitcnt vmcnt(5) lgkmcnt(0)")
             st.raw("s_barrier")
             st.flush_lds()
-            for k, (text, rid) in enumerate(dk_row_reads(V, A, nxt, 0)):
-                slots.setdefault(48 + k // 2, []).insert(k % 2, (text, rid))
-        dma_at_gap(st, g, (49, 51, 53, 55, 57), ops, adv)
+            put(96, dk_row_reads(V, A, nxt, 0))
+        if g in DK_DMA_GAPS:    # one piece, then the advance of its own source offset
+            i = DK_DMA_GAPS.index(g)
+            dma_issue(st, ops[i:i + 1], adv[i:i + 1])
         for text, rid in slots.get(g, []):
             st.emit(text, lds_id=rid)
         text, deps = mf[g]
@@ -696,12 +731,11 @@ def emit_dk_iter(st: Stream, V, A, stage, valu):
 
 
 def emit_dk_tail(st: Stream, V, A, valu):
-    nm = 64
     st.comment("---- tail: the last tile's second G group")
     st.raw("s_waitcnt lgkmcnt(0)")
     st.flush_lds()
-    # the last tile's trailing softmax: the VALU of slots 0..DK_START-1 (they wrapped)
-    rest = [t for i, t in enumerate(valu) if DK_START + (i * nm) // len(valu) >= nm]
+    # the last tile's trailing softmax: the groups of gaps 0..DK_START-1 (they wrapped)
+    rest = [t for i, grp in enumerate(valu) if DK_START + i >= DK_NM for t in grp]
     stage = 3
     for text, rid in dk_tr_reads(V, A, stage, 1):
         st.emit(text, lds_id=rid)
@@ -713,12 +747,17 @@ def emit_dk_tail(st: Stream, V, A, valu):
 
 def epilogue_dkdv(st: Stream, V, A):
     st.raw("s_waitcnt vmcnt(0)")
+    st.raw("s_lshl_b32 s99, s33, 4")   # 16 rows on: key tile jt = 1
     t = [V["s"] + k for k in range(8)]
     for name, rs, scale in (("adk", RDK2, "s44"), ("adv", RDV2, None)):
         for kj in range(2):
-            for i in range(2):
-                for g in range(4):
-                    base = 16 * (2 * i + kj) + 4 * g
+            for jt in range(2):
+                row = V.r("stk", kj)
+                if jt:
+                    row = f"v{t[6]}"
+                    st.emit(f"v_add_u32 {row}, s99, {V.r('stk', kj)}")
+                for dt in range(4):
+                    base = acc_idx(dt, kj, jt)
                     for k in range(4):
                         st.emit(f"v_accvgpr_read_b32 v{t[k]}, {A.r(name, base + k)}")
                     if scale:
@@ -726,8 +765,8 @@ def epilogue_dkdv(st: Stream, V, A):
                             st.emit(f"v_mul_f32 v{t[k]}, {scale}, v{t[k]}")
                     st.emit(f"v_cvt_pk_bf16_f32 v{t[4]}, v{t[0]}, v{t[1]}")
                     st.emit(f"v_cvt_pk_bf16_f32 v{t[5]}, v{t[2]}, v{t[3]}")
-                    st.emit(f"buffer_store_dwordx2 v[{t[4]}:{t[5]}], {V.r('stk', kj)}, {rs}, 0 "
-                            f"offen offset:{64 * i + 16 * g}")
+                    st.emit(f"buffer_store_dwordx2 v[{t[4]}:{t[5]}], {row}, {rs}, 0 "
+                            f"offen offset:{32 * dt}")
 
 
 def gen_dkdv():
