@@ -838,6 +838,44 @@ int vd_gelu_tanh(const void* x, void* y, int64_t n, int dtype, void* stream);
 int vd_gelu_tanh_bwd(const void* x, const void* dy, void* dx, int64_t n, int dtype,
                      void* stream);
 
+/* ---- clip quality metrics: per-frame MSE (PSNR) and SSIM, whole frame or weighted region
+ * (build extension, no reference counterpart: the reference scores nothing) ----
+ * x, y: two clips, contiguous [B][C][T][H][W] in `dtype` (a 4-D batch of images is T = 1), the
+ * layout the samplers return; a frame is the C planes of one (b, t).  weight: fp32 [T][H][W],
+ * >= 0, shared by batch and channel (the region; typically 1 - keep of masked sampling), or
+ * NULL: a weight of ones, with the same bits as one.
+ *   u          = clamp((v - lo) / (hi - lo), 0, 1): the data range is 1 (SSIM assumes
+ *                intensities >= 0; sampler outputs are in [-1, 1] and may overshoot).  No 8-bit
+ *                quantisation.
+ *   mse[b, t]  = sum_c sum_px w[t, px] (ux - uy)^2 / (C sum_px w[t, px]);  PSNR = -10 log10(mse)
+ *                is the caller's.
+ *   SSIM (Wang et al. 2004): window g (x) g, g the 11-tap Gaussian with sigma 1.5, normalised in
+ *   double and then rounded to fp32; VALID positions only, so a plane's map is (H - 10) x (W -
+ *   10) and no padding convention enters; K1 = 0.01, K2 = 0.03, L = 1; window-weighted (biased)
+ *   variances;
+ *     s = (2 mx my + C1) (2 cxy + C2) / ((mx^2 + my^2 + C1) (vx + vy + C2)) per position;
+ *   ssim[b, t] = sum_c sum_pos w s / (C sum_pos w), w taken at the window's centre pixel
+ *                (y + 5, x + 5).
+ *   wsum_px[t] = sum_px w,  wsum_valid[t] = sum_pos w (centres of valid positions).  A frame
+ *   whose weight sum is 0 gets NaN in mse resp. ssim; the sums let the caller average over the
+ *   frames that count.
+ * Outputs (fp32, every element overwritten): mse [B * T], ssim [B * T], wsum_px [T], wsum_valid
+ * [T]; ssim_map (may be NULL) [B * C * T][H - 10][W - 10], s before weighting.
+ * Method: one workgroup per (plane, 32 x 32 tile of map positions) stages the 42 x 42 patches in
+ * LDS as differences from the patch's centre pixel (variances as E[(x - p)^2] - E[x - p]^2, with
+ * the exact correction for the fp32 window's sum: E[x^2] - E[x]^2 in fp32 is wrong by ~1e-7
+ * against C2 = 9e-4 where frames are smooth), runs the separable window and reduces in a fixed
+ * order into one record per (plane, tile) of `workspace` (vd_clip_metrics_workspace_size bytes,
+ * 4-byte aligned, may be uninitialised); a second launch, one workgroup per (b, t), adds the
+ * records in index order.  No atomics, no memset: the same bits eager and replayed from a HIP
+ * graph.  Rows need no alignment.  H < 11 or W < 11, a NULL pointer (weight and ssim_map
+ * excepted), hi <= lo, non-positive sizes and an unknown dtype fail before any launch. */
+size_t vd_clip_metrics_workspace_size(int B, int C, int T, int H, int W);
+int vd_clip_metrics(const void* x, const void* y, const float* weight, float lo, float hi, int B,
+                    int C, int T, int H, int W, int dtype, float* mse, float* ssim,
+                    float* wsum_px, float* wsum_valid, float* ssim_map, void* workspace,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

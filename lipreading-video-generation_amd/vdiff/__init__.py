@@ -13,3 +13,12 @@ from .schedulers import (CosineNoiseScheduler, DDIMSampler, LinearNoiseScheduler
                          LinearNoiseSchedulerV2)
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # vdiff.metrics (clip quality metrics) is also a command line, `python -m vdiff.metrics`:
+    # imported on first use, so that runpy does not find it loaded before it runs it
+    if name == "metrics":
+        import importlib
+        return importlib.import_module(".metrics", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -195,6 +195,9 @@ _SIGS = {
     "vd_mse_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _sz, _vp]),
     "vd_mse_loss_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
     "vd_gelu_tanh_bwd": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
+    "vd_clip_metrics_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
+    "vd_clip_metrics": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

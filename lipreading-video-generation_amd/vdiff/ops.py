@@ -814,6 +814,61 @@ def diffusion_loss(pred, x0, eps, t, sqrt_acp, sqrt_1m_acp, prediction="eps", we
     return (loss, per) if return_per_sample else loss
 
 
+SSIM_WINDOW = 11  # vd_clip_metrics: valid positions only, a plane's map is (H - 10) x (W - 10)
+
+
+def clip_metrics(x, y, weight=None, value_range=(-1, 1), want_map=False):
+    """Per-frame MSE and SSIM of two clips (vd_clip_metrics; the definition is in
+    include/vdiff.h): x, y contiguous [B, C, T, H, W] (or [B, C, H, W]: T = 1) of one shape and
+    dtype, fp32 or bf16, mapped to u = clamp((v - lo) / (hi - lo), 0, 1) inside the kernel;
+    weight: fp32 [T, H, W] ([H, W] for 4-D clips) >= 0 shared by batch and channel, or None (a
+    weight of ones, bit for bit).  Returns a namespace of device tensors, fp32: mse, ssim [B, T];
+    wsum_px, wsum_valid [T] (the weight over the pixels, and over the centres of the valid
+    window positions; a frame where it is 0 has NaN in mse resp. ssim); ssim_map [B, C, T, H - 10,
+    W - 10] (without T for 4-D clips) with want_map, else None.  No synchronisation; workspace
+    and outputs are allocated uninitialised (the call overwrites every element)."""
+    _gpu(x, y, weight)
+    if x.shape != y.shape or x.dtype != y.dtype or x.dim() not in (4, 5):
+        raise ValueError(f"clip_metrics: two clips [B, C, T, H, W] or [B, C, H, W] of one shape "
+                         f"and dtype, got {x.dtype} {tuple(x.shape)} and {y.dtype} "
+                         f"{tuple(y.shape)}")
+    four = x.dim() == 4
+    B, C = x.shape[:2]
+    T = 1 if four else x.shape[2]
+    H, W = x.shape[-2:]
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError(f"clip_metrics: frames of {H} x {W} are smaller than the "
+                         f"{SSIM_WINDOW} x {SSIM_WINDOW} SSIM window")
+    if min(B, C, T) < 1:
+        raise ValueError(f"clip_metrics: empty clip {tuple(x.shape)}")
+    try:
+        lo, hi = (float(v) for v in value_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"clip_metrics: value_range {value_range!r}: a (lo, hi) pair") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError(f"clip_metrics: value_range ({lo}, {hi}) needs finite lo < hi")
+    dt = _dtype(x)
+    x, y = _flat(x), _flat(y)
+    if weight is not None:
+        if tuple(weight.shape) != (T, H, W) and not (four and tuple(weight.shape) == (H, W)):
+            raise ValueError(f"clip_metrics: weight {tuple(weight.shape)} for frames and pixels "
+                             f"{(T, H, W)}")
+        if weight.dtype != torch.float32:
+            raise TypeError(f"clip_metrics: weight must be float32, got {weight.dtype}")
+        weight = _flat(weight)
+    dev = x.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    mse, ssim = torch.empty(B, T, **f32), torch.empty(B, T, **f32)
+    wpx, wvalid = torch.empty(T, **f32), torch.empty(T, **f32)
+    mshape = (B, C, H - 10, W - 10) if four else (B, C, T, H - 10, W - 10)
+    smap = torch.empty(mshape, **f32) if want_map else None
+    nws = _lib.lib().vd_clip_metrics_workspace_size(B, C, T, H, W)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _lib.call("vd_clip_metrics", _p(x), _p(y), _p(weight), lo, hi, B, C, T, H, W, dt, _p(mse),
+              _p(ssim), _p(wpx), _p(wvalid), _p(smap), _p(ws), _stream(x))
+    return SimpleNamespace(mse=mse, ssim=ssim, wsum_px=wpx, wsum_valid=wvalid, ssim_map=smap)
+
+
 def linear(x, weight, bias=None, residual=None):
     """x [..., Cin] @ weight[Cout, Cin]^T + bias (+ residual [..., Cout], fused into the
     epilogue) on the implicit-GEMM kernel (1x1 conv)."""

@@ -7,6 +7,7 @@
                    [--window-batch N]
                    [--known clip.npy [--keep-mask mask.npy | --generate-box Y0 Y1 X0 X1
                                       --keep-frames K --mask-feather PX]]
+                   [--score] [--score-against truth.npy] [--score-out metrics.json]
 
 Reference API kept (importable without running anything, unlike the reference script):
   * `config` -- the dict of test.py:33-49 (same keys; `ldm_params` may also carry the
@@ -247,7 +248,26 @@ def parse(argv=None):
                          "0 1)")
     ap.add_argument("--mask-feather", type=int, default=None, metavar="PX",
                     help="linear ramp of PX pixels just inside the box edges")
+    ap.add_argument("--score", action="store_true",
+                    help="PSNR and SSIM of the sample (--sampler ddim|dpm++) against the --known "
+                         "clip, frame by frame: over the whole frame and, weighted with 1 - keep, "
+                         "over the generated region (kept pixels ARE the known clip, so the "
+                         "whole-frame score flatters); written to --score-out")
+    ap.add_argument("--score-against", default=None, metavar="FILE.npy",
+                    help="score against this ground-truth clip instead, float in [-1, 1], shaped "
+                         "like the sample without its batch axis; needs no masked sampling")
+    ap.add_argument("--score-out", default=None, metavar="FILE.json",
+                    help="where the per-frame values and their means go (default "
+                         "<out-dir>/metrics.json)")
     args = ap.parse_args(argv)
+    scoring = args.score or args.score_against is not None
+    if args.score and args.known is None and args.score_against is None:
+        ap.error("--score needs --known or --score-against: a clip to score the sample against")
+    if args.score_out is not None and not scoring:
+        ap.error("--score-out needs --score or --score-against")
+    if scoring and args.image_size < 11:
+        ap.error(f"--score and --score-against need frames of at least 11 x 11, the SSIM window "
+                 f"(got --image-size {args.image_size})")
     box_flags = [f for f, v in (("--generate-box", args.generate_box),
                                 ("--keep-frames", args.keep_frames),
                                 ("--mask-feather", args.mask_feather)) if v is not None]
@@ -257,6 +277,9 @@ def parse(argv=None):
     if args.known is not None and args.sampler not in ("ddim", "dpm++"):
         ap.error(f"--known needs --sampler ddim or dpm++ (got {args.sampler}: the known clip is "
                  "kept inside their step kernel)")
+    if scoring and args.sampler not in ("ddim", "dpm++"):
+        ap.error(f"--score and --score-against need --sampler ddim or dpm++ (got {args.sampler}: "
+                 "the final x0 of their sampling drivers is what is scored)")
     if args.keep_mask is not None and box_flags:
         ap.error(f"--keep-mask excludes {', '.join(box_flags)}")
     if args.keep_frames is not None and args.keep_frames < 0:
@@ -326,6 +349,49 @@ def _load_mask(args, shape):
     return dict(known=torch.from_numpy(known).float()[None], keep=keep)
 
 
+def _load_target(args, shape):
+    """The ground-truth clip of --score-against, [1, 3, [frames,] H, W] fp32 on the CPU."""
+    gt = np.load(args.score_against, allow_pickle=False)
+    if tuple(gt.shape) != tuple(shape[1:]) or not np.issubdtype(gt.dtype, np.floating):
+        raise SystemExit(f"test.py: --score-against holds {gt.dtype} {tuple(gt.shape)}; the "
+                         f"sample is float {tuple(shape[1:])}")
+    if not (np.isfinite(gt).all() and np.abs(gt).max() <= 1.0):
+        raise SystemExit("test.py: --score-against has values outside [-1, 1]")
+    return torch.from_numpy(gt).float()[None]
+
+
+def score_sample(args, x0, mask, target=None):
+    """--score / --score-against: PSNR and SSIM of the final x0 against `target` (default: the
+    known clip of `mask`), whole frame and, with a mask, over the generated region (weight 1 -
+    keep).  Writes the report to --score-out and, beside the frames, what it scored: sample.npy
+    (the fp32 x0 in [-1, 1] without its batch axis) and score_weight.npy (the region weight), so
+    that `python -m vdiff.metrics sample.npy truth.npy [--weight score_weight.npy]` gives the
+    same numbers.  Returns the report."""
+    import json
+
+    from vdiff import metrics
+    sample = x0.detach().float().contiguous()
+    against = "score-against" if target is not None else "known"
+    truth = (mask["known"] if target is None else target).to(sample.device).float().contiguous()
+    os.makedirs(args.out_dir, exist_ok=True)
+    np.save(os.path.join(args.out_dir, "sample.npy"), sample[0].cpu().numpy())
+    report = {"against": against, "sampler": args.sampler, "steps": args.steps}
+    whole = metrics.clip_metrics(sample, truth)
+    metrics.print_report(whole, f"whole frame, against --{against}:")
+    report["whole"] = whole.to_json()
+    if mask:
+        weight = metrics.region_weight(mask["keep"])
+        np.save(os.path.join(args.out_dir, "score_weight.npy"), weight.cpu().numpy())
+        region = metrics.clip_metrics(sample, truth, weight=weight)
+        metrics.print_report(region, "generated region (weight 1 - keep):")
+        report["region"] = region.to_json()
+    path = args.score_out or os.path.join(args.out_dir, "metrics.json")
+    with open(path, "w") as f:
+        json.dump(report, f, indent=1)
+    print(f"metrics written to {path}")
+    return report
+
+
 def main(argv=None):
     args = parse(argv)
     if not torch.cuda.is_available():
@@ -382,20 +448,24 @@ def main(argv=None):
             if (i + 1) % args.save_every == 0 or i == sampler.steps - 1:
                 save_frame(x0, os.path.join(args.out_dir, f"x0_{i}"))
 
+        scoring = args.score or args.score_against is not None
         if clip_frames > frames:  # (--dims 3: _check_long)
             shape = (1, 3, clip_frames, args.image_size, args.image_size)
+        mask = _load_mask(args, shape)
+        target = _load_target(args, shape) if args.score_against is not None else None
+        if clip_frames > frames:
             _, x0 = sample_long(model, sampler, cond, audio, shape, window=frames,
                                 stride=args.window_stride, blend=args.window_blend,
                                 window_batch=args.window_batch, generator=g, callback=cb,
                                 guidance_scale=args.guidance_scale,
-                                guidance_rescale=args.guidance_rescale,
-                                **_load_mask(args, shape))
-            print("All images have been processed and saved.")
-            return x0
-        _, x0 = sample(model, sampler, cond, audio, shape, generator=g, callback=cb,
-                       guidance_scale=args.guidance_scale,
-                       guidance_rescale=args.guidance_rescale, **_load_mask(args, shape))
+                                guidance_rescale=args.guidance_rescale, **mask)
+        else:
+            _, x0 = sample(model, sampler, cond, audio, shape, generator=g, callback=cb,
+                           guidance_scale=args.guidance_scale,
+                           guidance_rescale=args.guidance_rescale, **mask)
         print("All images have been processed and saved.")
+        if scoring:
+            score_sample(args, x0, mask, target)
         return x0
     return sample_images(model, scheduler, cond, audio, n_timesteps=args.steps or 500,
                          out_dir=args.out_dir, save_every=args.save_every, generator=g,
