@@ -1693,7 +1693,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_fwd_defer_kernel(
     constexpr int SG = decltype(sg_c)::value;
     const char* cur = SG >= 0 ? smem + SG * STAGE_BYTES : nullptr;
     const char* prv = SG >= 0 ? smem + ((SG + NST - 1) % NST) * STAGE_BYTES : nullptr;
-    vm_wait_barrier<(PD - 1) * PER_TILE>();  // tile t landed; tile t-2 no longer read
+    // tile t landed; tile t-2 no longer read.  The lgkmcnt(0) is needed: in the stage-unrolled
+    // copies the compiler sinks the last PV MFMAs of step t-1, and the waits for their V reads
+    // of tile t-2, below this barrier, while issue(t + PD) refills exactly that stage
+    // (profiles/ring_barriers.md)
+    vm_lgk_wait_barrier<(PD - 1) * PER_TILE>();
     issue(t + PD);
     const int b0 = 2 * t;
     if constexpr (LATE) V(sb, pb, psb, b0 - 1, std::false_type{});

@@ -124,7 +124,22 @@ __device__ __forceinline__ uint32_t lds_addr(const char* p) {
 // The LDS-DMA is issued from inline asm on purpose: the compiler's waitcnt pass cannot tell
 // which LDS bytes a builtin buffer_load...lds writes, so it put an s_waitcnt vmcnt(0) in
 // front of the first LDS read after it -- draining the whole ring every tile.  The ring's
-// own counted vmcnt + s_barrier (vm_wait_barrier) is what orders these writes.
+// own counted vmcnt + s_barrier is what orders these writes against the reads of a stage.
+// Two forms of that barrier (below), and which ring uses which (profiles/ring_barriers.md is
+// the reading of every one of them in the gfx950 ISA):
+//  - vm_wait_barrier: waits for the DMA only.  Enough where, in the compiled code, every
+//    ds_read of the stage refilled next is already waited for before the barrier: the
+//    runtime-trip-count loops, whose consuming MFMAs (and the compiler's lgkmcnt waits in front
+//    of them) sit before the back-edge -- igemm_dma_kernel (conv.hip), wgrad_dma_kernel,
+//    attention's tile_loop -- and tile_pipe (attention.hip: the pipelined backward), where the
+//    reads left in flight across an unrolled step's barrier are of the tile the next step still
+//    reads, not of the stage refilled.  That is a property of the schedule, not of the source:
+//    read the ISA again after a compiler change or a change to those loops.
+//  - vm_lgk_wait_barrier: also waits for this wave's own LDS reads.  Needed where the compiler
+//    sinks MFMAs, and their waits, below the asm barrier while those reads are of the stage
+//    refilled next: the tap-unrolled halo conv and wgrad_strip_kernel (conv.hip, round 6: seen
+//    as bits that changed from launch to launch) and the stage-unrolled attn_fwd_defer_kernel
+//    (attention.hip: found in the ISA).  Costs nothing where the reads had returned anyway.
 // M0 (the LDS destination) is an input operand bound with the "{m0}" constraint: the
 // compiler itself writes M0 and knows this statement reads it, so it never keeps a value
 // of its own there across the DMA.

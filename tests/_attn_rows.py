@@ -278,5 +278,19 @@ SELF_CASES = [
 # seeds were taken from the emulation on the CPU (1.37e-2 and 1.21e-2), before any kernel ran.
 
 
+# Ring-depth cases of tests/test_gpu_ring_determinism.py: sequences of 64 and 79 key tiles (5000:
+# a ragged last tile and a tile count that is no multiple of the 4 ring stages), so that the
+# stage-unrolled ring loops run many rounds on a grid of many workgroups.
+# (B, C, heads, T, HW, mode, seed, amp); the head-dim-32 row runs with legacy True and False.
+# The seeds were checked against CAP with the emulation on the CPU before any kernel ran
+# (tests/test_bounds_host.py).
+RING_SELF_CASES = [(1, C, 1, 1, N, "joint", 500 + C + N, 1.0)
+                   for N in (4096, 5000) for C in (64, 128)] + [
+    (1, 128, 4, 1, 4096, "joint", 540, 1.0),   # head dim 32: the generic kernels
+]
+# (B, C, heads, T, HW, L, per_frame, seed, amp): clip level, 16 * 40 = 640 keys = 10 key tiles
+RING_CROSS_CASES = [(1, 64, 1, 16, 1024, 40, False, 550, 1.0)]
+
+
 def case_id(c):
     return "-".join(str(v) for v in c)

@@ -77,6 +77,67 @@ def test_assert_elementwise_reports_and_handles_edges():
         assert_elementwise(torch.tensor([1.0, -2.0, 1e-30]), ref, mag, 1, True)
 
 
+# ------------------------------------------- the sampled conv reference of the ring tests
+@pytest.mark.parametrize("case", [6, 7], ids=["stride122", "dims2"])
+def test_conv_ref64_at_equals_the_full_references(case):
+    """conv_ref64_at (crops only) against conv_fwd_ref64 / conv_bwd_ref64 (the whole conv) at
+    the same indices, to 1e-12 of the element's magnitude and of the largest value: a row of
+    test_gpu_conv_bounds.CASES with stride (1, 2, 2) (the dx window holds 1 or 2 outputs per
+    strided dim) and a 2-D one, with bias, chan_add and residual.  The sample holds every corner
+    and face, so the zero padding of the crops is compared too."""
+    from test_gpu_conv_bounds import CASES
+    from _bounds import (conv_bwd_ref64, conv_ref64_at, gather_pixels, sample_channels,
+                         sample_pixels)
+    shape, Co, k, stride, pad, _ = CASES[case]
+    assert (case == 6 and stride == (1, 2, 2)) or (case == 7 and len(shape) == 4)
+    nd, Ci = len(shape) - 2, shape[1]
+    x = bf16r(seeded(shape, 1))
+    w = bf16r(seeded((Co, Ci) + (k,) * nd, 2) / (Ci * k ** nd) ** 0.5)
+    b = 0.1 * seeded((Co,), 3)
+    ref, mag, n = conv_fwd_ref64(x, w, b, stride, pad)
+    ca = seeded((shape[0], Co), 4)
+    res = bf16r(seeded(tuple(ref.shape), 5))
+    ref, mag, n = conv_fwd_ref64(x, w, b, stride, pad, ca, res)
+    dy = bf16r(seeded(tuple(ref.shape), 6))
+    dx, dxm, n_dx, dw, dwm, n_dw = conv_bwd_ref64(x, w, dy, stride, pad)
+    y_pix = sample_pixels((shape[0],) + tuple(ref.shape[2:]), 64, 7)
+    x_pix = sample_pixels((shape[0],) + tuple(shape[2:]), 64, 8, parity=True)
+    if case == 6:
+        assert {(int(h) % 2, int(v) % 2) for h, v in x_pix[:, -2:]} == {(0, 0), (0, 1), (1, 0),
+                                                                         (1, 1)}
+    cos, cis = sample_channels(Co, 8, 9), sample_channels(Ci, 8, 10)
+    assert 0 in cos and Co - 1 in cos and 63 in cis and len(cos) >= 8 and len(cis) >= 8
+    got = conv_ref64_at(x, w, b, dy, stride, pad, y_pix, x_pix, cos, cis, ca, res)
+    want = {"y": (gather_pixels(ref, y_pix), gather_pixels(mag, y_pix), n),
+            "dx": (gather_pixels(dx, x_pix), gather_pixels(dxm, x_pix), n_dx),
+            "dw": (dw[cos][:, cis], dwm[cos][:, cis], n_dw)}
+    for name in ("y", "dx", "dw"):
+        (r, m, nt), (wr, wm, wn) = got[name], want[name]
+        assert nt == wn and r.shape == wr.shape and r.dtype == torch.float64, name
+        assert bool(((r - wr).abs() <= 1e-12 * wm).all()), name
+        assert bool(((m - wm).abs() <= 1e-12 * wm).all()), name
+        assert float((r - wr).abs().max()) <= 1e-12 * float(wr.abs().max()), name
+
+
+def test_sample_pixels_holds_the_required_points():
+    """At least n pixels, no duplicates, all 8 corners, both ends of the first / middle / last
+    128-row tile."""
+    from _bounds import sample_pixels
+    dims = (1, 4, 91, 90)
+    pix = sample_pixels(dims, 256, 3)
+    rows = {tuple(int(v) for v in r) for r in pix}
+    assert len(rows) == len(pix) >= 256
+    for t in (0, 3):
+        for h in (0, 90):
+            for v in (0, 89):
+                assert (0, t, h, v) in rows
+    total = 4 * 91 * 90
+    flat = {(r[1] * 91 + r[2]) * 90 + r[3] for r in rows}
+    nt = (total + 127) // 128
+    for t in (0, nt // 2, nt - 1):
+        assert t * 128 in flat and min(t * 128 + 127, total - 1) in flat
+
+
 # ------------------------------------------- the fp64 references of the GPU bound tests
 def test_groupnorm_reference_matches_autograd():
     """gn_ref (tests/test_gpu_groupnorm_bounds.py) in fp64 against torch's own GroupNorm (+ SiLU)
@@ -233,6 +294,27 @@ def test_attention_gpu_cross_cases_keep_the_emulation_cap(case):
     import _attn_rows as A
     _, _, _, host = A.cross_inputs(*case)
     print(case, host.emu_stat)
+    host.assert_cap()
+
+
+def _ring_case_params():
+    import _attn_rows as A
+    return [pytest.param(c, legacy, id=A.case_id(c) + f"-legacy{int(legacy)}")
+            for c in A.RING_SELF_CASES for legacy in ((True, False) if c[2] > 1 else (True,))] + [
+        pytest.param(c, None, id="cross-" + A.case_id(c)) for c in A.RING_CROSS_CASES]
+
+
+@pytest.mark.parametrize("case,legacy", _ring_case_params())
+def test_attention_gpu_ring_cases_keep_the_emulation_cap(case, legacy):
+    """Every case of tests/test_gpu_ring_determinism.py (N = 4096 / 5000 self-attention, head
+    dims 32 / 64 / 128, and the 640-key clip-level cross-attention): the same cap."""
+    import _attn_rows as A
+    if legacy is None:
+        _, _, _, host = A.cross_inputs(*case)
+    else:
+        B, C, heads, T, HW, mode, seed, amp = case
+        _, _, host = A.self_inputs(B, C, T, HW, mode, seed, amp, heads, legacy)
+    print(case, legacy, host.emu_stat)
     host.assert_cap()
 
 
